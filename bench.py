@@ -9,12 +9,17 @@ all-reduce of the 840-f64 payload (RCCL over xGMI for N>1) and the IW/Q update o
 Hypotheses are sharded one per GPU (weak scaling): `value` counts hypothesis-scans of the whole
 job; the multi-hypothesis node's scans/s is `scans_per_s_node` (= value / n_gpus).
 
-Besides the headline line (C2 = BASELINE.json configs[1]) the same run measures, on rank 0 at N=1:
-the roofline kernel at C3 (configs[2], `roofline_c3`), the pinned-host H2D of one raw scan
-(`host_ms.h2d`), and the numpy oracle on the host cores (`cpu_baseline`: 1 core, all cores, and
-the C1-equivalent N=8192 x B=48 dense case).
+A plain run sets up, warms up, times the K steps and prints the headline line (C2 = BASELINE.json
+configs[1]) with what the timed region itself yields (per-step distribution, host split, the roofline
+kernel's stamped launches).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy.  `--full` adds, after the timed region, every measurement that takes runs of its own:
+the step variants, the all-stage diagnostic pass (`stage_ms`, `roofline_chain`), the pinned-host H2D
+of one raw scan (`host_ms.h2d`) and, on rank 0 at N=1, the roofline kernel at C3 (configs[2],
+`roofline_c3`), the live primitive path (`live_path`) and the numpy oracle on the host cores
+(`cpu_baseline`: 1 core, all cores, and the C1-equivalent N=8192 x B=48 dense case).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3] [--no-cpu-baseline] [--no-c3]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3] [--dump-outputs DIR]
+                       [--full [--no-cpu-baseline] [--no-c3] [--no-live]]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N, or plain
 `python bench.py --gpus N`: without a launcher's WORLD_SIZE this process starts the N rank processes
 itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, 127.0.0.1) before touching any GPU, and exits
@@ -278,6 +283,52 @@ def pmc_traffic(config):
         return None, None
     d = json.load(open(path))
     return d.get("hbm_bytes_per_launch"), f"profiles/pmc_bins_{config}.json ({d.get('round', 'r01')})"
+
+
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_MAX_BYTES = 60_000_000  # the files of one dump together (under 64 MB, decimal or binary, with room to spare)
+DUMP_SEED = 0
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (name -> array) as DIR/<name>.npy, float32 where it is
+    float32 and float64 otherwise.  The dump stays under DUMP_MAX_BYTES: going from the smallest array
+    up, one is written whole while it fits an equal share of the bytes left; a larger one is written as
+    a sample of its flattened elements at sorted indices drawn without replacement from
+    default_rng(DUMP_SEED) -- the same indices in every run of the same shapes, so two builds' dumps
+    compare element for element.  Returns name -> [elements written, elements of the array]."""
+    os.makedirs(dirname, exist_ok=True)
+    items = []
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        items.append((name, np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)))
+    items.sort(key=lambda it: (it[1].nbytes, it[0]))
+    left = DUMP_MAX_BYTES - 256 * len(items)  # (the .npy headers)
+    written = {}
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=k, replace=False))
+            a, n_all = a.reshape(-1)[idx], a.size
+        else:
+            n_all = a.size
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = [int(a.size), int(n_all)]
+    return written
+
+
+def scan_output_arrays(out):
+    """The result arrays of a GcsScanOutputs record (stage_ms holds timings, not results)."""
+    from gcslam import _lib as L
+    X, stamp, z_lin, Lm, h = L.struct_to_arrays(out.belief)
+    res = {"scan_belief_X_anchor": X, "scan_belief_stamp_sec": np.array([stamp]), "scan_belief_z_lin": z_lin,
+           "scan_belief_L": Lm, "scan_belief_h": h}
+    for name, _ in out._fields_:
+        if name not in ("belief", "stage_ms"):
+            res["scan_" + name] = np.ctypeslib.as_array(getattr(out, name)).copy()
+    return res
 
 
 def c3_roofline(device, steps=16, warmup=3):
@@ -599,6 +650,10 @@ def primitive_path_main(args, rank, world, local_rank, pin):
     if shared and not lead and st["pending"] is not None:  # catch up with the lead's last update
         primitive_map_follow(am, st["pending"], cfg)
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:  # the belief the last timed call returned
+        b = st["belief"]
+        write_outputs(args.dump_outputs, {"belief_X_anchor": b.X_anchor, "belief_stamp_sec": np.array([b.stamp_sec]),
+                                          "belief_z_lin": b.z_lin, "belief_L": b.L, "belief_h": b.h})
     h = hashlib.sha256()
     for t in sorted(am.tile_ids):
         for k, v in sorted(am.read_tile(int(t)).items()):
@@ -777,9 +832,17 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c3", action="store_true")
-    ap.add_argument("--no-live", action="store_true", help="skip the live primitive path's timing (live_path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's scan outputs, "
+                         "belief, ScanBinStats and map) as DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the measurements that take runs of their own: step "
+                         "variants, the all-stage diagnostic pass, H2D, the C3 roofline, the live primitive path "
+                         "and the CPU baseline (--no-c3 / --no-live / --no-cpu-baseline drop single ones)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the numpy oracle's CPU baseline")
+    ap.add_argument("--no-c3", action="store_true", help="--full without the roofline kernel's pass at C3")
+    ap.add_argument("--no-live", action="store_true",
+                    help="--full without the live primitive path's timing (live_path)")
     ap.add_argument("--map-mode", default="own", choices=["own", "shared"],
                     help="own: a map per hypothesis (default); shared: one map, hypothesis 0's (rank 0 leads, "
                          "the other ranks replay its update: gcslam_hip.h GCS_MAP_FOLLOW); at one GPU the rank "
@@ -794,6 +857,8 @@ def main():
     ap.add_argument("--cpu-rehearsal", action="store_true",
                     help="launcher + payload exchange over gloo on CPU (test of the multi-rank path)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps takes a positive count of timed steps, --warmup a count of at least 0")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         # before any GPU call in this process
@@ -976,6 +1041,17 @@ def main():
     ms_sum, counts = ctx.stage_times(reset=True)
     bins_in_region = int(counts[2])
     ctx.enable_timing(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller holds after the last timed step (the streams are drained): the scan's output record,
+        # the combined belief, and the ScanBinStats and map it can read back
+        arrays = scan_output_arrays(scan_out)
+        X, stamp, z_lin, Lm, hv = ctx.get_belief()
+        arrays.update(belief_X_anchor=X, belief_stamp_sec=np.array([stamp]), belief_z_lin=z_lin, belief_L=Lm,
+                      belief_h=hv, scan_bin_stats=ctx.get_scan_stats())
+        arrays["map"], arrays["map_derived"] = ctx.get_map()
+        arrays["iw_nu"], arrays["iw_Psi"], arrays["iw_Q"] = ctx.iw_state()
+        dumped = write_outputs(args.dump_outputs, arrays)
 
     def side_loop(name):  # the same steps again, a variant of the step (not `value`)
         # its own warm-up after the switch (round 5's single 20-step mean met one stall: 0.241 vs 0.10 ms),
@@ -998,40 +1074,41 @@ def main():
             dist.barrier()
         variants[name + "_ms_per_step"] = (time.perf_counter() - ta) / args.steps * 1e3
         variants[name + "_median_ms"] = float(np.median(per) * 1e3)
-    # the decomposition of ms_per_step: without the roofline stamps, and (N = 1) with the host-only
-    # combine instead of the world-1 RCCL all-reduce -- what round 4's line measured
-    state["stamp"] = False
     variants = {}
-    side_loop("unstamped")
-    if fused is not None:  # the same step as two C calls (gcs_scan, then gcs_combine_allreduce)
-        state["fused"] = None
-        side_loop("two_call_unstamped")
-    if world == 1 and comm is not None:
-        state["combine"] = ctx.combine_call(None, w_iw, w_bary)
-        if fused is not None:
-            state["fused"] = ctx.scan_combine_call(scan_out, None, w_iw, w_bary)
-        side_loop("host_combine_unstamped")
-        state["combine"] = combine
-    state["fused"] = fused
-    # the step with the IMU / odometry branch on the device (k_imu_odom on its own stream
-    # beside the bin path's kernels) instead of the host C++ branch, same box, its own warm-up
-    try:
-        if os.environ.get("GCSLAM_BENCH_NO_DEVIO") == "1":
-            raise RuntimeError("skipped (GCSLAM_BENCH_NO_DEVIO=1)")
-        ctx.set_debug(L.DEBUG_DEVICE_IMU_ODOM, 1)
-    except (RuntimeError, ValueError) as e:  # an older library in a same-box A/B
-        variants["device_imu_odom_unstamped_error"] = str(e)[:200]
-    else:
+    if args.full:
+        # the decomposition of ms_per_step: without the roofline stamps, and (N = 1) with the host-only
+        # combine instead of the world-1 RCCL all-reduce -- what round 4's line measured
+        state["stamp"] = False
+        side_loop("unstamped")
+        if fused is not None:  # the same step as two C calls (gcs_scan, then gcs_combine_allreduce)
+            state["fused"] = None
+            side_loop("two_call_unstamped")
+        if world == 1 and comm is not None:
+            state["combine"] = ctx.combine_call(None, w_iw, w_bary)
+            if fused is not None:
+                state["fused"] = ctx.scan_combine_call(scan_out, None, w_iw, w_bary)
+            side_loop("host_combine_unstamped")
+            state["combine"] = combine
+        state["fused"] = fused
+        # the step with the IMU / odometry branch on the device (k_imu_odom on its own stream
+        # beside the bin path's kernels) instead of the host C++ branch, same box, its own warm-up
         try:
-            side_loop("device_imu_odom_unstamped")
-        finally:
-            ctx.set_debug(L.DEBUG_DEVICE_IMU_ODOM, 0)
-    state["stamp"] = True
+            if os.environ.get("GCSLAM_BENCH_NO_DEVIO") == "1":
+                raise RuntimeError("skipped (GCSLAM_BENCH_NO_DEVIO=1)")
+            ctx.set_debug(L.DEBUG_DEVICE_IMU_ODOM, 1)
+        except (RuntimeError, ValueError) as e:  # an older library in a same-box A/B
+            variants["device_imu_odom_unstamped_error"] = str(e)[:200]
+        else:
+            try:
+                side_loop("device_imu_odom_unstamped")
+            finally:
+                ctx.set_debug(L.DEBUG_DEVICE_IMU_ODOM, 0)
+        state["stamp"] = True
     if "main_thread_cpu" in pin:  # the share again (the C3 pass, the live path, the CPU baseline's processes)
         os.sched_setaffinity(threading.get_native_id(), set(share))
     # the roofline kernel's duration: the timed region's stamped launches (every TIMING_STRIDE-th scan)
-    # plus, when those are fewer than ROOFLINE_MIN (short runs), a pass stamping it on every scan
-    if bins_in_region < ROOFLINE_MIN:
+    # plus (--full), when those are fewer than ROOFLINE_MIN (short runs), a pass stamping it on every scan
+    if args.full and bins_in_region < ROOFLINE_MIN:
         ctx.enable_timing(True, stages=["bins"])
         for _ in range(ROOFLINE_MIN - bins_in_region):
             step()
@@ -1077,14 +1154,17 @@ def main():
     if world > 1:  # every rank's host split and combine latency, so SCALE can attribute a loss
         per_rank = [None] * world
         dist.all_gather_object(per_rank, me)
-    # diagnostic pass after the timed region: every device stage stamped (not part of `value`)
-    ctx.enable_timing(True)
-    for _ in range(min(args.steps, 20)):
-        step()
-    ctx.synchronize()
-    ms_sum, counts = ctx.stage_times(reset=True)
-    stage_avg = {name: (float(ms_sum[i] / counts[i]) if counts[i] else None) for i, name in enumerate(ctx.STAGES)}
-    ctx.enable_timing(False)
+    # --full: diagnostic pass after the timed region, every device stage stamped (not part of `value`)
+    stage_avg = None
+    if args.full:
+        ctx.enable_timing(True)
+        for _ in range(min(args.steps, 20)):
+            step()
+        ctx.synchronize()
+        ms_sum, counts = ctx.stage_times(reset=True)
+        stage_avg = {name: (float(ms_sum[i] / counts[i]) if counts[i] else None)
+                     for i, name in enumerate(ctx.STAGES)}
+        ctx.enable_timing(False)
     manifest = ctx.describe()
     ms_ = ctx.mirror_stats()
     mirror = dict(scan_mirrors=ms_[0], scan_rereads=ms_[1], scan_sync_fallbacks=ms_[2], allreduces=ms_[3],
@@ -1095,13 +1175,20 @@ def main():
 
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
-        h2d, h2d_bytes = h2d_ms(scans, device)
-        host_avg["h2d"] = h2d
+        pcie = None
+        if args.full:
+            h2d, h2d_bytes = h2d_ms(scans, device)
+            host_avg["h2d"] = h2d
+            pcie = {"h2d_bytes_per_scan": h2d_bytes, "scans_per_s": 1e3 / (ms_step / world + h2d) * world,
+                    "note": "not `value`: a caller holding the raw scan in pinned host memory adds one H2D"}
         line = {
             "metric": METRIC if args.config == "c2" else "scans/sec (14-step pipeline) at 256k pts/scan",
             "value": world * args.steps / elapsed, "unit": "scans/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64",
+            # --full fills step_variants, stage_ms, roofline_chain, host_ms.h2d, pcie_inclusive, roofline_c3,
+            # live_path and cpu_baseline (each a run of its own after the timed region); null or absent otherwise
+            "full": args.full, "outputs_dumped": dumped,
             "data": "synthetic (seeded VLP-16-like scans, box room, IMU 200 Hz, odometry; inputs resident in HBM)",
             "config": {"workload": f"{args.config}: {N}-pt scans vs {B}-bin map, K={K} candidates, "
                                    f"1 hypothesis per GPU ({world} hypotheses), payload all-reduce per scan"
@@ -1131,18 +1218,17 @@ def main():
             "roofline": dict(roofline(N, B, bins_ms, *pmc_traffic(args.config)) or {}, timed_launches=bins_samples,
                              timed_launches_in_region=bins_in_region, stamp_stride=TIMING_STRIDE),
             "roofline_chain": roofline_chain(N, B, stage_avg, f"{args.config} (diagnostic pass, every stage stamped)",
-                                             config=args.config),
+                                             config=args.config) if stage_avg else None,
             "stage_ms": stage_avg,
             "host_ms": host_avg,
-            "pcie_inclusive": {"h2d_bytes_per_scan": h2d_bytes, "scans_per_s": 1e3 / (ms_step / world + h2d) * world,
-                               "note": "not `value`: a caller holding the raw scan in pinned host memory adds one H2D"},
+            "pcie_inclusive": pcie,
             "manifest": manifest,
         }
-        if world == 1 and args.config == "c2" and not args.no_c3:
+        if args.full and world == 1 and args.config == "c2" and not args.no_c3:
             line["roofline_c3"], line["roofline_chain_c3"] = c3_roofline(local_rank)
-        if world == 1 and not args.no_live:
+        if args.full and world == 1 and not args.no_live:
             line["live_path"] = live_path_bench(local_rank)
-        line["cpu_baseline"] = cpu_baseline(cfg) if (world == 1 and not args.no_cpu_baseline) else None
+        line["cpu_baseline"] = cpu_baseline(cfg) if (args.full and world == 1 and not args.no_cpu_baseline) else None
         print(json.dumps(line), flush=True)
     if comm is not None:
         comm.close()
