@@ -127,6 +127,41 @@ class GcsSurfelOutputs(C.Structure):
                [("center", C.c_double * 3), ("n_valid", C.c_int32), ("cert", C.c_double * 2)]
 
 
+class GcsCamsplatConfig(C.Structure):
+    _fields_ = [("depth_fusion_weight_camera", C.c_double), ("depth_fusion_weight_lidar", C.c_double),
+                ("gamma_lidar", C.c_double), ("lidar_projection_radius_pix", C.c_double),
+                ("lidar_plane_fit_min_points", C.c_int32), ("lidar_depth_base_sigma_m", C.c_double),
+                ("lidar_incidence_sigma_scale", C.c_double), ("depth_var_min_m2", C.c_double),
+                ("point_support_n0", C.c_double), ("point_support_alpha", C.c_double),
+                ("spread_mad_beta", C.c_double), ("repr_gamma", C.c_double),
+                ("lidar_ray_plane_fit_max_points", C.c_int32), ("plane_intersection_delta", C.c_double),
+                ("plane_angle_sigmoid_alpha", C.c_double), ("plane_angle_sigmoid_t", C.c_double),
+                ("plane_planarity_sigmoid_beta", C.c_double), ("plane_planarity_rho0", C.c_double),
+                ("plane_residual_exp_gamma", C.c_double), ("plane_fit_eps", C.c_double), ("depth_min_m", C.c_double),
+                ("depth_sigma_max_sq", C.c_double), ("depth_min_sigmoid_alpha_z", C.c_double),
+                ("pixel_sigma", C.c_double), ("eps_lift", C.c_double), ("n_feat", C.c_int32), ("n_surfel", C.c_int32),
+                ("max_points", C.c_int32), ("max_candidates", C.c_int32), ("device", C.c_int32)]
+
+
+class GcsCamsplatInputs(C.Structure):
+    _fields_ = [("points_base", C.c_void_p), ("n_points", C.c_int32), ("R_base_camera", C.c_double * 9),
+                ("t_base_camera", C.c_double * 3), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("n_features", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("u", "v", "depth_Lambda_c", "depth_theta_c", "xyz", "cov", "weight",
+                                          "kappa_app", "mu_app", "has_mu", "color", "has_color")] + \
+               [("timestamp_sec", C.c_double)]
+
+
+CAMSPLAT_BATCH_FIELDS = ("Lambdas", "thetas", "etas", "weights", "sources", "source_indices", "valid_mask",
+                         "timestamps", "colors")
+CAMSPLAT_DIAG_FIELDS = ("n_pt", "z_med", "mad", "Lambda_A", "theta_A", "Lambda_B", "theta_B", "z_f", "fused")
+
+
+class GcsCamsplatOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in CAMSPLAT_BATCH_FIELDS + CAMSPLAT_DIAG_FIELDS] + \
+               [("n_camera_valid", C.c_int32)]
+
+
 GCS_ASSOC_CERT_LEN = 21
 ASSOC_CERT_FIELDS = ("marginal_defect_a", "marginal_defect_b", "transport_mass_total", "sum_a", "sum_b", "sum_m",
                      "sum_novel", "p95_a", "p95_b", "nonzero_a", "nonzero_b", "b_recency_p95", "ess_total",
@@ -333,6 +368,12 @@ _SIGS = [
     ("gcs_surfel_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("gcs_extract_lidar_surfels", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.POINTER(GcsSurfelOutputs)]),
+    ("gcs_camsplat_config_defaults", C.c_int, [C.POINTER(GcsCamsplatConfig)]),
+    ("gcs_camsplat_ctx_create", C.c_int, [C.POINTER(GcsCamsplatConfig), C.POINTER(C.c_void_p)]),
+    ("gcs_camsplat_ctx_destroy", C.c_int, [C.c_void_p]),
+    ("gcs_camsplat_last_error", C.c_char_p, [C.c_void_p]),
+    ("gcs_camsplat_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gcs_camera_splats", C.c_int, [C.c_void_p, C.POINTER(GcsCamsplatInputs), C.POINTER(GcsCamsplatOutputs)]),
     ("gcs_assoc_config_defaults", C.c_int, [C.POINTER(GcsAssocConfig)]),
     ("gcs_debug_short_log_exp", C.c_int, [c_double_p, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p]),
     ("gcs_debug_tab_log_exp", C.c_int, [c_double_p, C.c_int32, c_double_p, c_double_p]),

@@ -35,6 +35,7 @@ from .outputs import tape_from_result
 CHART_ID = "GC-RIGHT-01"
 D_Z = 22
 HYP_WEIGHT_FLOOR = 0.0025   # constants.py:63
+CAMERA_BATCH_POLICIES = ("warn", "raise", "ignore", "use")
 
 
 @dataclass
@@ -86,7 +87,9 @@ class PipelineConfig:
     planar_z_sigma: float = 0.1
     planar_vz_sigma: float = 0.01
     enable_imu_odom: bool = True      # False: LiDAR-only ablation (the reference always runs the branch)
-    camera_batch_policy: str = "warn"  # camera evidence is out of scope here: "warn" once | "raise" | "ignore"
+    # a non-empty camera_batch: "warn" once and drop it (default) | "raise" | "ignore" | "use": with a
+    # primitive map the batch's camera slice joins the scan's LiDAR surfels (gcslam.camera builds it)
+    camera_batch_policy: str = "warn"
     max_raw_points: int = 1 << 20
     device: int = 0
     # PipelineConfig.enable_timing (pipeline.py:380-394; default off, backend_node.py:152): the live
@@ -115,6 +118,11 @@ class PipelineConfig:
     N_STENCIL_TILES: int = 7
     RECENCY_DECAY_LAMBDA: float = 0.02
     RECENCY_MIN_SCALE: float = 0.05
+
+    def __post_init__(self):
+        if self.camera_batch_policy not in CAMERA_BATCH_POLICIES:
+            raise ValueError(f"camera_batch_policy {self.camera_batch_policy!r}: expected one of "
+                             f"{CAMERA_BATCH_POLICIES}")
 
     def context_kwargs(self) -> dict:
         return dict(n_bins=self.B_BINS, n_points_cap=self.N_POINTS_CAP, max_raw_points=self.max_raw_points,
@@ -182,6 +190,7 @@ class ScanPipelineResult:
     map_update_cert: Optional[MapUpdateCert] = None
     association: Optional[object] = None
     map_view: Optional[object] = None
+    visual_pose: Optional[object] = None  # the scan's VisualPoseEvidenceResult (its L_pose / h_pose: the LiDAR evidence)
     z_lin_pose: Optional[np.ndarray] = None
     map_record: Optional[dict] = None  # the map update's inputs (primitive_map_follow)
     stage_ms: Optional[dict] = None    # live path, config.enable_timing: wall ms per stage (synced)
@@ -356,15 +365,20 @@ def _camera_batch_has_content(camera_batch):
 def _process_scan_primitive(ctx: HypothesisContext, primitive_map, belief_prev, rec, t, w, imu_stamps, imu_gyro,
                             imu_accel, odom_pose, odom_cov_se3, scan_start_time, scan_end_time, dt_sec, t_last_scan,
                             t_scan, Q, config: PipelineConfig, odom_twist, odom_twist_cov, scan_seq, L_ext, h_ext,
-                            update_map=True):
+                            update_map=True, camera_batch=None):
     """The live pipeline (pipeline.py:316-1591) on the device: gcs_scan_begin (budget, predict, IMU
     preintegration, deskew, IMU/odometry branch, z_lin_pose) -> the map branch (:778-926) -> visual
     pose evidence (:980-1010) -> gcs_scan_finish (tempering, fusion, recompose, anchor drift) ->
-    step 12b at z_t (:1232-1492)."""
+    step 12b at z_t (:1232-1492).  camera_batch (camera_batch_policy "use"): the surfels join its camera
+    slice (extract_lidar_surfels(base_batch=...), pipeline.py:781-795); the one-call chain has no camera
+    rows, so such a scan takes the per-operator path."""
     import torch
     from . import association as GA, primitive_map as GPM
     from .surfels import SurfelExtractionConfig, extract_lidar_surfels
-    if _live_chain_enabled(ctx, config):
+    if camera_batch is not None and (camera_batch.n_feat != config.n_feat or camera_batch.n_surfel != config.n_surfel):
+        raise ValueError(f"camera_batch budgets ({camera_batch.n_feat}, {camera_batch.n_surfel}) differ from the "
+                         f"config's n_feat / n_surfel ({config.n_feat}, {config.n_surfel})")
+    if camera_batch is None and _live_chain_enabled(ctx, config):
         return _process_scan_live_chain(ctx, primitive_map, rec, t, w, imu_stamps, imu_gyro, imu_accel, odom_pose,
                                         odom_cov_se3, scan_start_time, scan_end_time, dt_sec, t_last_scan, t_scan, Q,
                                         config, odom_twist, odom_twist_cov, scan_seq, L_ext, h_ext, update_map)
@@ -394,8 +408,8 @@ def _process_scan_primitive(ctx: HypothesisContext, primitive_map, belief_prev, 
     scfg = SurfelExtractionConfig(n_surfel=config.n_surfel, n_feat=config.n_feat,
                                   voxel_size_m=config.surfel_voxel_size_m,
                                   min_points_per_voxel=config.surfel_min_points_per_voxel, eps_lift=config.eps_lift)
-    batch, c_surf, _ = extract_lidar_surfels(bufs[0], bufs[1], bufs[2], config=scfg, chart_id=CHART_ID,
-                                             device=config.device)
+    batch, c_surf, _ = extract_lidar_surfels(bufs[0], bufs[1], bufs[2], config=scfg, base_batch=camera_batch,
+                                             chart_id=CHART_ID, device=config.device)
     tick("surfel_extraction_ms")
     centre = np.array(b.pose_pred[:3])
     active = GPM.ma_hex_stencil_tile_ids(centre, config.H_TILE, config.R_ACTIVE_TILES_XY, config.R_ACTIVE_TILES_Z)
@@ -463,7 +477,8 @@ def _process_scan_primitive(ctx: HypothesisContext, primitive_map, belief_prev, 
     record = dict(active=[int(x) for x in active], scan_seq=int(scan_seq), t=float(scan_end_time), z_t=z_t,
                   batch=batch, association=res)
     return out, dict(map=am, batch=batch, map_update_cert=muc, certs=[c_surf, c_infl, c_assoc, c_vis],
-                     association=res, view=view, z_lin_pose=z_lin_pose, map_record=record, stage_ms=stage_ms)
+                     association=res, view=view, visual=vis, z_lin_pose=z_lin_pose, map_record=record,
+                     stage_ms=stage_ms)
 
 
 def _live_chain_enabled(ctx: HypothesisContext, config: "PipelineConfig") -> bool:
@@ -713,7 +728,7 @@ def _live_chain_results(ctx, am, st, lo, o_sf, bo, out, batch, vt, view_tids, a_
     record = dict(active=active, scan_seq=int(scan_seq), t=float(scan_end_time), z_t=z_t, batch=batch,
                   association=res)
     live = dict(map=am, batch=batch, map_update_cert=None, certs=[c_surf, c_infl, c_assoc, c_vis], association=res,
-                view=view, z_lin_pose=z_lin_pose, map_record=record, stage_ms={})
+                view=view, visual=vis, z_lin_pose=z_lin_pose, map_record=record, stage_ms={})
 
     def finish():
         if live["map_update_cert"] is not None:
@@ -774,10 +789,15 @@ def process_scan_single_hypothesis(belief_prev: BeliefGaussianInfo, raw_points, 
     preintegration, measurement-noise statistics, IMU evidence), odometry pose / covariance /
     twist (the step-9 odometry factors; None takes the node's "no odometry yet" inputs,
     backend_node.py:939-940,2047-2051).  raw_ring / raw_tag are only gathered by the reference's
-    budget step for the primitive path; the bin path does not read them.  camera_batch feeds the
-    live primitive path's visual evidence, which this backend does not build (DESIGN.md out of
-    scope): config.camera_batch_policy says whether a non-empty batch warns (default), raises or is
-    ignored.  L_ext / h_ext add further caller evidence to step 9.
+    budget step for the primitive path; the bin path does not read them.  camera_batch (a
+    MeasurementBatch whose camera slice is filled, gcslam.camera.camera_batch_from_features) feeds the
+    live primitive path: config.camera_batch_policy says whether a non-empty batch warns and is dropped
+    (default), raises, is ignored, or is used.  "use" with a primitive_map hands it to
+    extract_lidar_surfels(base_batch=camera_batch) (pipeline.py:781-795): association, pose evidence
+    and map update then see camera splats and LiDAR surfels together, and result.measurement_batch
+    carries both slices.  Such a scan runs operator by operator: the one-call gcs_live_scan chain has
+    no camera rows.  On the bin path (no primitive_map) nothing consumes the batch and "use" warns
+    like "warn".  L_ext / h_ext add further caller evidence to step 9.
 
     primitive_map (an AtlasMap): the live primitive path (pipeline.py:778-1011, 1232-1492) replaces the
     bin evidence; map_bins then only carries the hypothesis state (belief, IW), and result.map is the
@@ -788,10 +808,13 @@ def process_scan_single_hypothesis(belief_prev: BeliefGaussianInfo, raw_points, 
     a result.map is valid until then (copy it -- AtlasMap.working_copy -- to keep it longer).
     result.map_record holds the update's inputs for primitive_map_follow (one map over several GPUs)."""
     global _camera_warned
+    use_camera = None
     if _camera_batch_has_content(camera_batch):
         if config.camera_batch_policy == "raise":
             raise NotImplementedError("camera_batch: visual evidence is not part of the bin-path backend")
-        if config.camera_batch_policy == "warn" and not _camera_warned:
+        if config.camera_batch_policy == "use" and primitive_map is not None:
+            use_camera = camera_batch
+        elif config.camera_batch_policy in ("warn", "use") and not _camera_warned:
             warnings.warn("camera_batch ignored: the bin-path backend has no visual evidence (DESIGN.md section 9)")
             _camera_warned = True
     _stamp("enter")
@@ -804,7 +827,7 @@ def process_scan_single_hypothesis(belief_prev: BeliefGaussianInfo, raw_points, 
         out, live = _process_scan_primitive(ctx, primitive_map, belief_prev, rec, t, w, imu_stamps, imu_gyro,
                                             imu_accel, odom_pose, odom_cov_se3, scan_start_time, scan_end_time, dt_sec,
                                             t_last_scan, t_scan, Q, config, odom_twist, odom_twist_cov, scan_seq,
-                                            L_ext, h_ext, update_map=update_map)
+                                            L_ext, h_ext, update_map=update_map, camera_batch=use_camera)
     else:
         out = ctx.scan(rec, 4 * rec.shape[1], t, w, rec.shape[0], imu_stamps, imu_gyro, imu_accel, scan_start_time, scan_end_time,
                        dt_sec, Q=Q, L_ext=L_ext, h_ext=h_ext, t_last_scan=t_last_scan, t_scan=t_scan,
@@ -851,6 +874,7 @@ def _scan_result(ctx, out, live, belief_prev, scan_seq, scan_end_time, dt_sec, n
         res.map_update_cert = live["map_update_cert"]
         res.association = live["association"]
         res.map_view = live["view"]
+        res.visual_pose = live["visual"]
         res.z_lin_pose = live["z_lin_pose"]
         res.map_record = live["map_record"]
         res.stage_ms = live["stage_ms"]

@@ -36,6 +36,9 @@
  *   gcs_extract_lidar_surfels   FS/backend/operators/lidar_surfel_extraction.py:339-431
  *                               extract_lidar_surfels (+ FS/common/ma_hex_web.py:243-303
  *                               bin_points_3d, FS/backend/structures/measurement_batch.py:272-381)
+ *   gcs_camera_splats           FS/frontend/sensors/lidar_camera_depth_fusion.py + splat_prep.py:37-134
+ *                               (lidar_depth_evidence, splat_prep_fused), FS/backend/backend_node.py:
+ *                               1872-1925, FS/backend/structures/measurement_batch.py:165-259
  */
 #ifndef GCSLAM_HIP_H
 #define GCSLAM_HIP_H
@@ -589,6 +592,91 @@ int gcs_surfel_ctx_set_stream(gcs_surfel_ctx* ctx, void* stream);
 /* points: n x 3 f64, timestamps / weights: n f64 (device); n <= max_points.  Synchronises. */
 int gcs_extract_lidar_surfels(gcs_surfel_ctx* ctx, const double* points_dev, const double* timestamps_dev,
                               const double* weights_dev, int32_t n, gcs_surfel_outputs* out);
+
+/* ---------------------------------------------------------------- primitive path: camera splats */
+/* The camera half of the node's per-scan batch (backend_node.py:1865-1925) on the GPU: LiDAR points
+ * to the camera frame and the image (lidar_camera_depth_fusion.py:80-96), per visual feature the
+ * LiDAR depth evidence along its pixel ray -- Route A, the robust depth sample of the points within
+ * lidar_projection_radius_pix (:99-164), and Route B, the ray / plane intersection with the plane
+ * of the nearest points (:242-386) -- the product of experts with the camera's depth
+ * (splat_prep.py:37-134), the back-projection with its closed-form covariance (:450-489), the move
+ * to the base frame (backend_node.py:1887-1918) and rows [0, n_feat) of the MeasurementBatch in
+ * information form (camera_batch_utils.py:23-86, measurement_batch.py:165-259).  Route B's plane
+ * fits are uniformly weighted (splat_prep_fused passes no point weights).  A context owns the
+ * workspace for up to max_points points on one GPU; calls on one context must be serialised. */
+typedef struct gcs_camsplat_ctx gcs_camsplat_ctx;
+
+typedef struct {
+  /* LidarCameraDepthFusionConfig (lidar_camera_depth_fusion.py:29-63), same names and defaults */
+  double depth_fusion_weight_camera, depth_fusion_weight_lidar, gamma_lidar;
+  double lidar_projection_radius_pix;
+  int32_t lidar_plane_fit_min_points;
+  double lidar_depth_base_sigma_m, lidar_incidence_sigma_scale, depth_var_min_m2;
+  double point_support_n0, point_support_alpha, spread_mad_beta, repr_gamma;
+  int32_t lidar_ray_plane_fit_max_points;   /* at most 64: one lane of a wave per fitted point */
+  double plane_intersection_delta, plane_angle_sigmoid_alpha, plane_angle_sigmoid_t;
+  double plane_planarity_sigmoid_beta, plane_planarity_rho0, plane_residual_exp_gamma, plane_fit_eps;
+  double depth_min_m, depth_sigma_max_sq, depth_min_sigmoid_alpha_z;
+  /* splat_prep_fused / feature_list_to_camera_batch arguments */
+  double pixel_sigma;            /* splat_prep.py:43 (1.0) */
+  double eps_lift;               /* GC_EPS_LIFT */
+  int32_t n_feat, n_surfel;      /* the batch's budgets: the call writes rows [0, n_feat) */
+  int32_t max_points;            /* capacity of the context (points per call) */
+  int32_t max_candidates;        /* points within the radius of one feature held at once (<= 1024) */
+  int32_t device;
+} gcs_camsplat_config;
+
+/* One call's inputs.  Pointers are device arrays (f64 unless noted); extrinsics, intrinsics and the
+ * batch's timestamp are host values. */
+typedef struct {
+  const double* points_base;     /* n_points x 3, base frame (gcs_scan_begin's deskewed points) */
+  int32_t n_points;
+  double R_base_camera[9], t_base_camera[3];   /* p_base = R p_camera + t */
+  double fx, fy, cx, cy;
+  int32_t n_features;            /* M */
+  const double *u, *v;           /* M pixel coordinates */
+  const double *depth_Lambda_c, *depth_theta_c;   /* M: the camera's depth in natural form (0: none) */
+  const double *xyz, *cov;       /* M x 3, M x 9: camera-frame splat, kept where fusion does not apply */
+  const double *weight, *kappa_app;   /* M */
+  const double* mu_app;          /* M x 3 (camera frame) */
+  const uint8_t* has_mu;         /* M: 0 = the view direction xyz / |xyz| takes mu_app's place */
+  const double* color;           /* M x 3 RGB */
+  const uint8_t* has_color;      /* M: 0 = grey 0.5 */
+  double timestamp_sec;
+} gcs_camsplat_inputs;
+
+/* Outputs: device pointers.  The batch arrays have n_feat rows (the camera slice) and are all written:
+ * rows [0, n_camera_valid) from the first min(M, n_feat) features, the rest zeros.  The per-feature
+ * diagnostics (M rows) may each be NULL. */
+typedef struct {
+  double* Lambdas;         /* n_feat x 9   inv(Sigma_base + eps_lift I) */
+  double* thetas;          /* n_feat x 3 */
+  double* etas;            /* n_feat x 3 lobes x 3: lobe 0 = kappa_app * direction */
+  double* weights;         /* n_feat */
+  int32_t* sources;        /* n_feat       0 = camera */
+  int32_t* source_indices; /* n_feat */
+  uint8_t* valid_mask;     /* n_feat */
+  double* timestamps;      /* n_feat */
+  double* colors;          /* n_feat x 3   clipped to [0, 1] */
+  int32_t* n_pt;           /* M  points within the radius */
+  double *z_med, *mad;     /* M  Route A's median depth and MAD (NaN below lidar_plane_fit_min_points) */
+  double *Lambda_A, *theta_A, *Lambda_B, *theta_B;   /* M  lidar_depth_evidence's return_diag */
+  double* z_f;             /* M  fused depth (0 where the input splat is kept) */
+  uint8_t* fused;          /* M  1 = fused, 0 = the input splat kept (splat_prep.py:85-93) */
+  /* host result */
+  int32_t n_camera_valid;  /* min(M, n_feat) */
+} gcs_camsplat_outputs;
+
+int gcs_camsplat_config_defaults(gcs_camsplat_config* cfg);
+int gcs_camsplat_ctx_create(const gcs_camsplat_config* cfg, gcs_camsplat_ctx** out);
+int gcs_camsplat_ctx_destroy(gcs_camsplat_ctx* ctx);
+const char* gcs_camsplat_last_error(const gcs_camsplat_ctx* ctx);
+/* stream: a hipStream_t (NULL = the context's own); work on it is ordered after the caller's */
+int gcs_camsplat_ctx_set_stream(gcs_camsplat_ctx* ctx, void* stream);
+/* Synchronises.  GCS_ERR_STATE when a feature has more than max_candidates points within its radius
+ * (the message names the first such feature): every batch row is then zero / invalid and
+ * n_camera_valid 0 -- nothing is truncated silently. */
+int gcs_camera_splats(gcs_camsplat_ctx* ctx, const gcs_camsplat_inputs* in, gcs_camsplat_outputs* out);
 
 /* ---------------------------------------------------------------- primitive path: OT association */
 /* associate_primitives_ot (primitive_association.py:239-553) on the GPU: per measurement the MA-hex
