@@ -111,7 +111,6 @@ struct gcs_ctx {
   bool counts_clean = false;
   bool flags_clean[2] = {false, false};
   bool pt_clear = true;  // GCSLAM_PT_CLEAR=0 / GCS_DEBUG_PT_CLEAR 0: k_budget clears as before (A/B)
-  int budget_max = 128;  // k_budget's block cap (GCSLAM_BUDGET_BLOCKS, 1..1024)
   int flags_cur = 0;
   uint8_t* d_touched = nullptr;     // per bin: the map holds mass (k_map_derive / k_pushforward)
   uint8_t* d_tile_dirty = nullptr;  // k_bins_scale: tile output not the zero-bin values (persistent)
@@ -120,16 +119,7 @@ struct gcs_ctx {
   int* d_tile_order = nullptr;
   uint32_t* d_tile_work = nullptr;
   bool tile_order_on = false;
-  // GCSLAM_TILE_ORDER_PUSH=1: k_tile_order deferred to the push stream behind the scan's
-  // pushforward (or onto the main stream ahead of the next bin kernel when no pushforward went out on
-  // its own stream).  Off: measured slower at C3 (0.2245 -> 0.2355 ms per step, profiles/r04/tod1/):
-  // on the main stream behind the PT fold it fills the device while the host runs the tail, the
-  // combine and the next prologue; behind the pushforward and its fold it ends after k_points and
-  // the next bin kernel waits for it.
-  bool tile_order_defer = false;
-  bool tile_order_pending = false;
   double* d_bins_part = nullptr;    // k_bins_scale partial rows (persistent: clean tiles keep theirs)
-  double* d_bins_raw = nullptr;     // split bin path: active bins' 19 raw sums (field-major; 128-bin tiles)
   double* d_scan = nullptr;
   double* d_map = nullptr;
   double* d_derived = nullptr;
@@ -149,7 +139,6 @@ struct gcs_ctx {
   hipEvent_t ev_stages = nullptr;
   bool stages_done = false;  // wait_mirror saw the scan's stages complete (no event wait for the push)
   bool push_pending = false;
-  bool push_main = false;  // experiment knob (GCSLAM_PUSH_MAIN=1): k_pushforward on the main stream
   // Asynchronous pushforward launch (GCSLAM_PUSH_THREAD=0 turns it off): the launch calls of
   // k_pushforward and its fold (~10 us of host time per scan, on the scan's critical path) are made
   // by a per-context worker thread; every later use of the map, the flags or the push event first
@@ -363,15 +352,10 @@ gcs_ctx::PushJob& claim_job(gcs_ctx* c) {
 // A pushforward whose event has already completed needs no stream wait: its writes are visible to
 // every later dispatch, and the wait's barrier packet costs the main queue a few µs (C2 trace: the
 // bin kernel started 6.5 µs after k_points ended behind an event that had fired 30 µs before).
-// GCSLAM_JOIN_WAIT=always: the stream wait on every scan.
 int join_push(gcs_ctx* c) {
-  static const bool always = [] {
-    const char* e = getenv("GCSLAM_JOIN_WAIT");
-    return e && strcmp(e, "always") == 0;
-  }();
   if (int rc = push_wait(c)) return rc;
   if (!c->push_pending) return GCS_OK;
-  if (always || hipEventQuery(c->ev_push) != hipSuccess) (void)hipStreamWaitEvent(c->stream, c->ev_push, 0);
+  if (hipEventQuery(c->ev_push) != hipSuccess) (void)hipStreamWaitEvent(c->stream, c->ev_push, 0);
   c->push_pending = false;
   return GCS_OK;
 }
@@ -384,15 +368,9 @@ int join_push(gcs_ctx* c) {
 
 constexpr int kRedBlocks = 1024;
 int red_blocks(long n) { return (int)std::max(1L, std::min((long)kRedBlocks, (n + 255) / 256)); }
-// k_pt's grid: GCSLAM_PT_BLOCKS caps it (default kRedBlocks: four bins per thread at C3)
-constexpr int kPtBlocksMax = 8192;
-int pt_blocks(long n) {
-  static const int cap = [] {
-    const char* e = getenv("GCSLAM_PT_BLOCKS");
-    return e ? std::max(1, std::min(kPtBlocksMax, atoi(e))) : kRedBlocks;
-  }();
-  return (int)std::max(1L, std::min((long)cap, (n + 255) / 256));
-}
+// k_pt's grid: capped at kRedBlocks (four bins per thread at C3)
+int pt_blocks(long n) { return red_blocks(n); }
+constexpr int kBudgetBlocksMax = 128;  // k_budget's block cap (stage_budget)
 
 // read back a stage's recorded event pairs (oldest first; each waits for its end event)
 void harvest_stage(gcs_ctx* c, int st) {
@@ -553,9 +531,9 @@ int stage_budget(gcs_ctx* c, const double* w, int n_raw, bool toggle = true, boo
     if (c->flags_clean[c->flags_cur]) ba.n_zero8 = 0;
     c->flags_clean[c->flags_cur] = false;
   }
-  // k_budget's grid: at most budget_max blocks (every k_points block folds all of its partial rows,
-  // and on a busy GPU -- the previous scan's pushforward -- each block waits for a CU slot)
-  c->budget_blocks = std::min(red_blocks(std::max(n_raw, 1)), c->budget_max);
+  // k_budget's grid: at most kBudgetBlocksMax blocks (every k_points block folds all of its partial
+  // rows, and on a busy GPU -- the previous scan's pushforward -- each block waits for a CU slot)
+  c->budget_blocks = std::min(red_blocks(std::max(n_raw, 1)), kBudgetBlocksMax);
   c->budget_pending = true;
   c->budget_self = self;
   if (self) {
@@ -688,7 +666,6 @@ BinKernelArgs bin_args(gcs_ctx* c) {
   b.n_bins = c->B;
   b.cap = c->cap;
   b.tile_bins = c->tile_bins;
-  b.raw = c->d_bins_raw;
   memcpy(b.origin, c->cfg.lidar_origin, 3 * sizeof(double));
   b.tau = c->cfg.tau;
   b.scan = c->d_scan;
@@ -708,10 +685,8 @@ BinKernelArgs bin_args(gcs_ctx* c) {
   return b;
 }
 
-int flush_tile_order(gcs_ctx* c, hipStream_t s, gcs_ctx* ec);
 int stage_bins(gcs_ctx* c) {
   hipStream_t s = c->stream;
-  if (int rc = flush_tile_order(c, s, c)) return rc;  // (a tile order no pushforward took)
   BinKernelArgs b = bin_args(c);
   if (c->cfg.mode == GCS_MODE_SCALE) {
     if (!c->use_direct) {  // sorted bucketing (direct buckets: k_points placed and flagged them)
@@ -769,7 +744,7 @@ void take_mirror_err(gcs_ctx* c) {
 // checksum of what it reads matches: a buffer whose data words have not all reached host memory when
 // the sequence word has is re-read (*rereads), never consumed.  Without a valid buffer after 20 ms (a
 // fault, or a stalled queue) the stream synchronize waits and reports the asynchronous error (*syncs),
-// and the buffer must then be complete.  GCSLAM_SYNC_WAIT=stream: synchronize only.
+// and the buffer must then be complete.
 uint64_t stamped_sum(const volatile uint64_t* m, int n) {
   uint64_t s = 0;
   for (int i = 0; i < n; ++i) s += mirror_word_hash(m[i], (uint32_t)i);
@@ -778,29 +753,23 @@ uint64_t stamped_sum(const volatile uint64_t* m, int n) {
 
 int wait_stamped(gcs_ctx* c, const double* buf, int n, uint64_t seq, hipStream_t stream, int64_t* rereads,
                  int64_t* syncs, const char* what) {
-  static const bool spin = [] {
-    const char* e = getenv("GCSLAM_SYNC_WAIT");
-    return !(e && strcmp(e, "stream") == 0);
-  }();
   const volatile uint64_t* m = reinterpret_cast<const volatile uint64_t*>(buf);
-  if (spin) {
-    const auto t0 = clk::now();
-    bool reread = false;
-    for (;;) {
-      if (m[n] == seq) {
+  const auto t0 = clk::now();
+  bool reread = false;
+  for (;;) {
+    if (m[n] == seq) {
+      std::atomic_thread_fence(std::memory_order_acquire);
+      if (stamped_sum(m, n) == m[n + 1]) {
         std::atomic_thread_fence(std::memory_order_acquire);
-        if (stamped_sum(m, n) == m[n + 1]) {
-          std::atomic_thread_fence(std::memory_order_acquire);
-          if (reread) ++*rereads;
-          return GCS_OK;
-        }
-        reread = true;  // the sequence word is here, some data word is not yet: read again
+        if (reread) ++*rereads;
+        return GCS_OK;
       }
-      __builtin_ia32_pause();
-      if (clk::now() - t0 > std::chrono::milliseconds(20)) break;
+      reread = true;  // the sequence word is here, some data word is not yet: read again
     }
-    ++*syncs;
+    __builtin_ia32_pause();
+    if (clk::now() - t0 > std::chrono::milliseconds(20)) break;
   }
+  ++*syncs;
   HIPCHK(c, hipStreamSynchronize(stream));
   if (m[n] != seq || stamped_sum(m, n) != m[n + 1])
     return fail(c, GCS_ERR_HIP, std::string(what) + ": sequence " + std::to_string((unsigned long long)m[n]) +
@@ -855,22 +824,14 @@ int stage_pt(gcs_ctx* c, bool to_host = false, bool clear_next = false) {
 // the next scan's bin-tile dispatch order from this scan's bin kernel (d_tile_dirty / d_tile_work ->
 // d_tile_order; read only by the next bin kernel, written by nothing else), queued on the main stream
 // behind the scan's stages: the device runs it while the host runs the tail (the next bin kernel is
-// behind it in stream order).  Deferred (GCSLAM_TILE_ORDER_PUSH=1, measured slower): the scan's
-// pushforward takes it onto the push stream behind itself (stage_push, after the stages) and the next
-// bin kernel is ordered after it by join_push; a scan whose pushforward does not go out on its own
-// stream leaves it pending, and the next stage_bins queues it on the main stream.
-int flush_tile_order(gcs_ctx* c, hipStream_t s, gcs_ctx* ec) {
-  if (!c->tile_order_pending) return GCS_OK;
-  c->tile_order_pending = false;
-  HIPCHK(ec, launch_tile_order(c->d_tile_dirty, c->d_tile_work, bins_scale_blocks(c->B, c->tile_bins), c->d_tile_order,
-                               s));
-  return GCS_OK;
-}
+// behind it in stream order).  (Deferring it to the push stream behind the scan's pushforward measured
+// slower at C3: 0.2245 -> 0.2355 ms per step, profiles/r04/tod1/ -- behind the pushforward and its fold
+// it ends after k_points and the next bin kernel waits for it.)
 int stage_tile_order(gcs_ctx* c) {
   if (!c->tile_order_on) return GCS_OK;
-  c->tile_order_pending = true;
-  if (c->tile_order_defer && !c->push_main && c->push_stream) return GCS_OK;
-  return flush_tile_order(c, c->stream, c);
+  HIPCHK(c, launch_tile_order(c->d_tile_dirty, c->d_tile_work, bins_scale_blocks(c->B, c->tile_bins), c->d_tile_order,
+                              c->stream));
+  return GCS_OK;
 }
 
 // on_worker: called by the push worker; errors are returned, not written to the context's message
@@ -897,16 +858,13 @@ int stage_push(gcs_ctx* c, const double* z_t, const double* Sig6, double gamma, 
   StageEv ev = stage_ev(c, ST_PUSH);
   // the main stream's stages are complete once wait_mirror saw the fold's ready word (the fold is
   // the stream's last kernel before it): only the other paths order the push stream by the event.
-  // k_tile_order runs on the main stream after that fold, where it may run beside this pushforward
-  // (or behind it on the same stream, GCSLAM_TILE_ORDER_PUSH=1): it reads d_tile_dirty / d_tile_work
-  // and writes d_tile_order, and the pushforward reads d_scan / d_flags and writes d_map / d_derived /
+  // k_tile_order runs on the main stream after that fold, where it may run beside this pushforward:
+  // it reads d_tile_dirty / d_tile_work and writes d_tile_order, and the pushforward reads d_scan / d_flags and writes d_map / d_derived /
   // d_touched / its partials and map-total scalars -- disjoint buffers, which the two must keep.  A fault in k_tile_order is reported by the
   // next call that synchronises its stream.
   if (s != c->stream && !c->stages_done) HIPCHK(ec, hipStreamWaitEvent(s, c->ev_stages, 0));
   HIPCHK(ec, launch_pushforward(c->d_scan, c->d_map, c->d_derived, c->B, pa, partials, c->d_scalars, flags,
                                c->d_touched, s, ev.e0, ev.e1));
-  // the deferred tile order behind it (the stages it reads are complete, as for the pushforward)
-  if (int rc = flush_tile_order(c, s, ec)) return rc;
   if (s != c->stream) {
     HIPCHK(ec, hipEventRecord(c->ev_push, s));
     c->push_pending = true;
@@ -1204,24 +1162,13 @@ int gcs_ctx_create(const gcs_config* cfg, gcs_ctx** out) {
     return false;
   };
   if (bad(hipSetDevice(cfg->device))) return GCS_ERR_HIP;
-  // GCSLAM_STREAM_PRIO=1: the scan stages' stream at the device's highest priority and the pushforward's
-  // at its lowest, so the next scan's front takes the CUs the previous pushforward frees (A/B knob)
-  {
-    const char* e = getenv("GCSLAM_STREAM_PRIO");
-    int lo = 0, hi = 0;
-    if (e && atoi(e) != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) {
-      if (bad(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi))) return GCS_ERR_HIP;
-      c->own_stream = true;
-      if (bad(hipStreamCreateWithPriority(&c->push_stream, hipStreamNonBlocking, lo))) return GCS_ERR_HIP;
-    } else {
-      if (bad(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking))) return GCS_ERR_HIP;
-      c->own_stream = true;
-      if (bad(hipStreamCreateWithFlags(&c->push_stream, hipStreamNonBlocking))) return GCS_ERR_HIP;
-    }
-  }
+  // (stream priorities -- the scan stages' stream highest, the pushforward's lowest -- measured neutral:
+  // DESIGN.md section 5)
+  if (bad(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking))) return GCS_ERR_HIP;
+  c->own_stream = true;
+  if (bad(hipStreamCreateWithFlags(&c->push_stream, hipStreamNonBlocking))) return GCS_ERR_HIP;
   if (bad(hipEventCreateWithFlags(&c->ev_push, hipEventDisableTiming))) return GCS_ERR_HIP;
   if (bad(hipEventCreateWithFlags(&c->ev_stages, hipEventDisableTiming))) return GCS_ERR_HIP;
-  if (const char* pm = getenv("GCSLAM_PUSH_MAIN")) c->push_main = atoi(pm) != 0;
   if (const char* pt = getenv("GCSLAM_PUSH_THREAD")) c->push_async = atoi(pt) != 0;
   if (const char* sb = getenv("GCSLAM_SORTED_BUCKETS")) c->direct_buckets = atoi(sb) == 0;
   const size_t B = c->B, cap = c->cap;
@@ -1269,7 +1216,6 @@ int gcs_ctx_create(const gcs_config* cfg, gcs_ctx** out) {
   if (const char* g = getenv("GCSLAM_PT_CLEAR")) c->pt_clear = atoi(g) != 0;
   if (const char* g = getenv("GCSLAM_BEGIN_MIRROR")) c->begin_mirror = atoi(g) != 0;
   if (const char* g = getenv("GCSLAM_LIVE_ASYNC")) c->live_async = atoi(g) != 0;
-  if (const char* g = getenv("GCSLAM_BUDGET_BLOCKS")) c->budget_max = std::max(1, std::min(1024, atoi(g)));
   if (bad(hipHostMalloc(&c->h_preint_out, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent)))
     return GCS_ERR_HIP;
   if (cfg->mode == GCS_MODE_SCALE) {
@@ -1302,8 +1248,6 @@ int gcs_ctx_create(const gcs_config* cfg, gcs_ctx** out) {
       const int nt = bins_scale_blocks(c->B, c->tile_bins);
       const char* e = getenv("GCSLAM_TILE_ORDER");
       c->tile_order_on = nt > 2048 && !(e && atoi(e) == 0);
-      const char* ep = getenv("GCSLAM_TILE_ORDER_PUSH");
-      c->tile_order_defer = ep && atoi(ep) == 1;
       if (c->tile_order_on) {
         std::vector<int> ident(nt);
         for (int i = 0; i < nt; ++i) ident[i] = i;
@@ -1315,16 +1259,9 @@ int gcs_ctx_create(const gcs_config* cfg, gcs_ctx** out) {
     }
     if (bad(hipMalloc(&c->d_bins_part, partials_need(bins_scale_blocks(c->B, c->tile_bins), bins_partial_nv()) * sizeof(double))))
       return GCS_ERR_HIP;
-    // the split bin path's raw sums (128-bin tiles, GCSLAM_BINS_SPLIT=1; default: the fused phase D).
-    // Same-box A/B at C3 (profiles/r06/split/): split 94 us (gather + finalize) against 84 us fused --
-    // the 19 raw sums of every active bin written and read back (~2 x 90 MB) cost more than the
-    // two-wave finalize they free
-    static const bool split = [] {
-      const char* e = getenv("GCSLAM_BINS_SPLIT");
-      return e && atoi(e) == 1;
-    }();
-    if (split && c->tile_bins == 128 && bad(hipMalloc(&c->d_bins_raw, (size_t)19 * B * sizeof(double))))
-      return GCS_ERR_HIP;
+    // (a split bin path -- the gather writing every active bin's 19 raw sums, phase D as its own
+    // bin-parallel kernel -- measured slower at C3, profiles/r06/split/: 94 us against 84 us fused; the
+    // raw sums written and read back, ~2 x 90 MB, cost more than the two-wave finalize they free)
   } else {
     size_t nchunks = (cap + 255) / 256;
     if (bad(hipMalloc(&c->d_bin_partials, nchunks * 19 * B * sizeof(double)))) return GCS_ERR_HIP;
@@ -1371,7 +1308,7 @@ int gcs_ctx_destroy(gcs_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   void* ptrs[] = {c->d_gate_xi, c->d_members, c->d_bin_dirs, c->d_knn, c->d_rknn_off, c->d_rknn, c->d_pools, c->d_pool_bound, c->d_recs, c->d_iz, c->d_live_p0, c->d_live_w, c->d_live_t, c->d_keys, c->d_slots,
                   c->d_sorted, c->d_nearest, c->d_counts, c->d_starts, c->d_perm, c->d_flags_buf[0], c->d_touched,
-                  c->d_tile_dirty, c->d_tile_order, c->d_tile_work, c->d_bins_part, c->d_bins_raw, c->d_tickets,
+                  c->d_tile_dirty, c->d_tile_order, c->d_tile_work, c->d_bins_part, c->d_tickets,
                   c->d_bin_ref, c->d_tile_src_off, c->d_tile_src, c->d_rknn_local, c->d_part_pts, c->d_mass_rows, c->d_part_push, c->d_parse_flag,
                   c->d_scan, c->d_map, c->d_derived, c->d_bin_partials, c->d_partials, c->d_scalars};
   for (void* p : ptrs)
@@ -1564,13 +1501,7 @@ int gcs_ctx_enable_timing(gcs_ctx* c, int32_t stage_mask) {
       c->ev[st].resize(2 * gcs_ctx::kEvRing, nullptr);
       // timing only: no system-scope fence when a stamp completes (the fence's cache write-back and
       // invalidate measured ~8 us per stamped scan at C2, profiles/r05/stamp/)
-      static const unsigned fl = [] {  // A/B knob GCSLAM_STAMP_EVENT=default|device (fence-free by default)
-        const char* e = getenv("GCSLAM_STAMP_EVENT");
-        if (e && strcmp(e, "default") == 0) return (unsigned)hipEventDefault;
-        if (e && strcmp(e, "device") == 0) return (unsigned)hipEventReleaseToDevice;
-        return (unsigned)hipEventDisableSystemFence;
-      }();
-      for (hipEvent_t& e : c->ev[st]) HIPCHK(c, hipEventCreateWithFlags(&e, fl));
+      for (hipEvent_t& e : c->ev[st]) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
     }
   c->timing_mask = (uint32_t)stage_mask;
   return GCS_OK;
@@ -2373,9 +2304,7 @@ int scan_tail(gcs_ctx* c, gcs_scan_state& st, const LidarTerms& lt, gcs_scan_out
   memcpy(c->map_rec + 12, Sig6, 36 * sizeof(double));
   auto Tq = clk::now();
   if (push && c->map_mode != GCS_MAP_FOLLOW)  // a follower's map takes the lead's update (gcs_map_follow)
-    if (int rc = submit_push(c, z_t, Sig6, c->cfg.forgetting_factor, c->push_main ? c->stream : c->push_stream,
-                             c->d_part_push))
-      return rc;
+    if (int rc = submit_push(c, z_t, Sig6, c->cfg.forgetting_factor, c->push_stream, c->d_part_push)) return rc;
   auto Tr = clk::now();
   memcpy(out->z_t, z_t, sizeof(out->z_t));
   // 14 AnchorDriftUpdate (anchor_drift.py:93-191)
@@ -3089,13 +3018,9 @@ int gcs_combine_allreduce(gcs_ctx* c, void* comm, double w_iw, double w_bary, in
     if (!c->comm_stream) {
       // the device's highest priority: the combine's kernels are dispatched ahead of the pushforward
       // that was just queued on the push stream (same box, alternated, profiles/r05/rccl/: combine 32 ->
-      // 19 us in the C2 pipeline, 0.1275-0.1295 -> 0.1154-0.1161 ms per step; GCSLAM_COMBINE_PRIO=0)
-      static const bool prio = [] {
-        const char* e = getenv("GCSLAM_COMBINE_PRIO");
-        return !(e && atoi(e) == 0);
-      }();
+      // 19 us in the C2 pipeline, 0.1275-0.1295 -> 0.1154-0.1161 ms per step)
       int lo = 0, hi = 0;
-      if (prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
+      if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
         HIPCHK(c, hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, hi));
       else
         HIPCHK(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
@@ -3190,8 +3115,7 @@ int gcs_map_follow(gcs_ctx* c, const gcs_scan_inputs* in, const double* rec) {
     c->use_direct = false;
   }
   c->h_err[1] = 0u;
-  return submit_push(c, r + 6, r + 12, c->cfg.forgetting_factor, c->push_main ? c->stream : c->push_stream,
-                     c->d_part_push);
+  return submit_push(c, r + 6, r + 12, c->cfg.forgetting_factor, c->push_stream, c->d_part_push);
 }
 
 int gcs_hypothesis_barycenter(int32_t n, const double* Ls, const double* hs, const double* zs, const double* w,

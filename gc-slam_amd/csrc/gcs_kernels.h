@@ -162,10 +162,6 @@ struct BinKernelArgs {
   int mass_nrows;
   uint32_t* zero_after;  // bucketing scratch (mid-list length, look-back words) re-armed for the next scan
   int n_zero_after;
-  // split finalize (sparse maps, 128-bin tiles; round 6): the gather kernel leaves each active bin's 19
-  // raw sums here (field-major, 19 x B) and k_bins_finalize, one thread per bin at full occupancy, writes
-  // ScanBinStats, the Matrix-Fisher terms and the active tiles' partial rows.  Null: fused phase D.
-  double* raw;
   const int* tile_order;  // block -> tile (k_tile_order; null: identity)
   uint32_t* tile_work;    // per tile: records the tile staged (written for active tiles; may be null)
 };
@@ -184,7 +180,7 @@ struct PushArgs {
 hipError_t launch_parse(const ParseArgs& a, hipStream_t s);
 hipError_t launch_budget(const BudgetArgs& a, int nblk, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
 // fold: run k_points' cert fold now (else k_bins_scale block 0 folds it, BinKernelArgs.pts_partials)
-int points_blocks(long cap, bool scale);  // k_points grid (lanes per point in scale mode)
+int points_blocks(long cap, bool scale);  // k_points grid
 int points_max_blocks();
 // IMU window weights + preintegration on the device (gcs_preint.hip; imu_preintegration.py:20-147)
 struct PreintArgs {

@@ -268,36 +268,15 @@ __device__ __forceinline__ int cube_cell(double dx, double dy, double dz, int G)
 // loads are issued in independent batches (whole pool row, whole candidate row) so the chain is
 // xyz -> pool ids -> pool dirs -> knn row -> candidate dirs -> slot atomic, and the softmax
 // evaluates one exp per candidate and no per-candidate log (entropy identity below).
-// LP > 1 (scale mode): LP lanes per point.  Each lane scans every LP-th chunk of the pool row and
-// takes KC/LP of the candidates, so the chain's load batches are LP times narrower per lane and
-// the register file holds KC/LP candidate terms; the lanes' nearest bins meet in a (dot, lower
-// id) max, their softmax terms in fixed xor trees (identical on every lane of the point).  One
-// lane per point takes the slot atomic and writes the record.
-#ifndef GCS_POINT_WAVES
-#define GCS_POINT_WAVES 0  // register target (waves per SIMD) of k_points; 0: compiler default
-#endif
-#ifndef GCS_PROBE_NOPOOL
-#define GCS_PROBE_NOPOOL 0
-#endif
-#ifndef GCS_PROBE_NOFLAGS
-#define GCS_PROBE_NOFLAGS 0  // timing probe (not a parity build): no first-arrival flag stores
-#endif
-#ifndef GCS_CAND_GROUP
-#define GCS_CAND_GROUP 16  // candidate direction loads in flight per group (16: all at once)
-#endif
+// One lane per point (2 and 4 lanes per point measured slower).
 // KC == 0 (!SCALE): deskew only -- the live primitive path's point stage (pipeline.py:399-418,
 // 568-587): budget gather, deskew, window weights and the budget / deskew certificate partials, no
 // soft assign and no record (the surfel extraction reads p0_out / w_out / t_out).
-template <bool SCALE, int KC, int LP>
+template <bool SCALE, int KC>
 __global__ __launch_bounds__(kBlock)
-#if GCS_POINT_WAVES
-__attribute__((amdgpu_waves_per_eu(GCS_POINT_WAVES)))
-#endif
 void k_points(PointKernelArgs a, double* partials) {
-  static_assert(LP == 1 || (SCALE && (LP == 2 || LP == 4) && KC % LP == 0), "lanes per point");
-  constexpr int KL = KC / LP, kPB = kBlock / LP;  // candidates per lane, points per block
-  constexpr int kCandGroup = KL < GCS_CAND_GROUP ? (KL > 0 ? KL : 1) : GCS_CAND_GROUP;
-  const int sub = threadIdx.x % LP;
+  // candidate direction loads in flight per group (16: all at once)
+  constexpr int kCandGroup = KC < 16 ? (KC > 0 ? KC : 1) : 16;
   __shared__ double lds[kWaves * 5];
   __shared__ double s_mass[2];
   // budget mass sums: every block folds k_budget's partial rows itself (same fixed order in every
@@ -327,10 +306,10 @@ void k_points(PointKernelArgs a, double* partials) {
   double msum[2] = {0.0, 0.0};
   if (self) mass_scale = 1.0;
   // uniform trip count (the budget fold inside the first iteration has barriers)
-  const int gstride = gridDim.x * kPB;
+  const int gstride = gridDim.x * kBlock;
   const int niter = (a.cap + gstride - 1) / gstride;
   for (int it = 0; it < niter; ++it) {
-    const int i = blockIdx.x * kPB + (int)threadIdx.x / LP + it * gstride;
+    const int i = blockIdx.x * kBlock + (int)threadIdx.x + it * gstride;
     const bool live = i < a.cap;
     double p[3] = {0.0, 0.0, 0.0}, t = 0.0, w_raw = 0.0;
     bool valid = live && i < a.n_sel;
@@ -345,7 +324,7 @@ void k_points(PointKernelArgs a, double* partials) {
       }
       t = a.timestamps[src];
       w_raw = a.weights[src];
-      if (self && sub == 0) {
+      if (self) {
         double wall = w_raw;
         for (int q = 1; q < a.stride && src + q < (size_t)a.n_raw; ++q) wall += a.weights[src + q];
         msum[0] += wall;
@@ -375,13 +354,11 @@ void k_points(PointKernelArgs a, double* partials) {
         const float* pbound = a.pool_bound + prow;
         const int nq = a.pool_width >> 2;
         double best = -INFINITY;
-        // 4 * CH ids per batch and lane: all loads in flight together
-        constexpr int CH = LP >= 4 ? 1 : 2;
-        // GCS_PROBE_NOPOOL (timing probe, not a parity build): the first pool id only
-        for (int q = sub; q < (GCS_PROBE_NOPOOL ? 1 : nq); q += CH * LP) {
+        // 8 ids per batch: all loads in flight together
+        for (int q = 0; q < nq; q += 2) {
           int4 u0 = pool[q];
-          int4 u1 = CH == 2 && q + LP < nq ? pool[q + LP] : make_int4(-1, -1, -1, -1);
-          const int qn = q + CH * LP;  // this lane's next batch
+          int4 u1 = q + 1 < nq ? pool[q + 1] : make_int4(-1, -1, -1, -1);
+          const int qn = q + 2;  // the next batch
           const float bnext = qn < nq ? pbound[4 * qn] : -2.0f;
           int ids[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
           double s[8];
@@ -389,13 +366,13 @@ void k_points(PointKernelArgs a, double* partials) {
           // batch's loads went out one round trip at a time); padding ids (-1) read bin 0 and
           // are masked to -inf after the loads
 #pragma unroll
-          for (int u = 0; u < 4 * CH; ++u) {
+          for (int u = 0; u < 8; ++u) {
             const double4 bd = *(const double4*)(a.bin_dirs + 4 * (size_t)(ids[u] >= 0 ? ids[u] : 0));
             const double sv = dot3_exact(d[0], d[1], d[2], bd.x, bd.y, bd.z);
             s[u] = ids[u] >= 0 ? sv : -INFINITY;
           }
 #pragma unroll
-          for (int u = 0; u < 4 * CH; ++u) {
+          for (int u = 0; u < 8; ++u) {
             if (s[u] > best) {
               best = s[u];
               nearest = ids[u];
@@ -405,31 +382,25 @@ void k_points(PointKernelArgs a, double* partials) {
           }
           // the bound is for unit directions and |d| < 1 (ray_dir divides by nrm + eps): it bounds the
           // scaled dot of a later entry only while best > 0 (always, for any atlas of >= 48 bins)
-          if ((CH == 2 ? u1.w : u0.w) < 0 || (best > 0.0 && (double)bnext < best)) break;
-        }
-#pragma unroll
-        for (int off = 1; off < LP; off <<= 1) {  // first maximum in reference-id order
-          const double ob = __shfl_xor(best, off, 64);
-          const int oi = __shfl_xor(nearest, off, 64);
-          if (ob > best || (ob == best && a.bin_ref[oi] < a.bin_ref[nearest])) { best = ob; nearest = oi; }
+          if (u1.w < 0 || (best > 0.0 && (double)bnext < best)) break;
         }
       }
-      int cand[KL];
-      if constexpr (KL % 4 == 0) {
-        const int4* cand4 = (const int4*)(a.knn + (size_t)nearest * KC + sub * KL);
+      int cand[KC];
+      if constexpr (KC % 4 == 0) {
+        const int4* cand4 = (const int4*)(a.knn + (size_t)nearest * KC);
 #pragma unroll
-        for (int k = 0; k < KL / 4; ++k) {
+        for (int k = 0; k < KC / 4; ++k) {
           int4 c4 = cand4[k];
           cand[4 * k] = c4.x; cand[4 * k + 1] = c4.y; cand[4 * k + 2] = c4.z; cand[4 * k + 3] = c4.w;
         }
       } else {
 #pragma unroll
-        for (int k = 0; k < KL; ++k) cand[k] = a.knn[(size_t)nearest * KC + sub * KL + k];
+        for (int k = 0; k < KC; ++k) cand[k] = a.knn[(size_t)nearest * KC + k];
       }
-      double e[KL];
-      // the candidates' directions in groups of GCS_CAND_GROUP loads in flight (x, y, z only: 24 B)
+      double e[KC];
+      // the candidates' directions in groups of kCandGroup loads in flight (x, y, z only: 24 B)
 #pragma unroll
-      for (int k0 = 0; k0 < KL; k0 += kCandGroup) {
+      for (int k0 = 0; k0 < KC; k0 += kCandGroup) {
         double3 bd[kCandGroup];
 #pragma unroll
         for (int k = 0; k < kCandGroup; ++k) {
@@ -442,23 +413,16 @@ void k_points(PointKernelArgs a, double* partials) {
           e[k0 + k] = dot3_exact(d[0], d[1], d[2], bd[k].x, bd[k].y, bd[k].z);
           m = fmax(m, e[k0 + k]);
         }
-        if (kCandGroup < KL) __builtin_amdgcn_sched_barrier(0);  // keep the groups apart (registers)
+        if (kCandGroup < KC) __builtin_amdgcn_sched_barrier(0);  // keep the groups apart (registers)
       }
-#pragma unroll
-      for (int off = 1; off < LP; off <<= 1) m = fmax(m, __shfl_xor(m, off, 64));
       // e_k = exp(x_k), x_k = (sim_k - m)/tau (binning.py:69 softmax, shifted by the max)
       double sxe = 0.0;
 #pragma unroll
-      for (int k = 0; k < KL; ++k) {
+      for (int k = 0; k < KC; ++k) {
         double x = (e[k] - m) * inv_tau;
         e[k] = exp(x);
         Z += e[k];
         sxe += x * e[k];
-      }
-#pragma unroll
-      for (int off = 1; off < LP; off <<= 1) {
-        Z += __shfl_xor(Z, off, 64);
-        sxe += __shfl_xor(sxe, off, 64);
       }
       const double iz = 1.0 / Z;
       // entropy of r_k = e_k/Z (binning.py:71-75): -sum r log(r + eps)
@@ -466,19 +430,14 @@ void k_points(PointKernelArgs a, double* partials) {
       // with r log1p(eps/r) in [0, eps] taken as eps r/(r + eps) (|error| < 0.2 eps per term)
       double corr = 0.0;
 #pragma unroll
-      for (int k = 0; k < KL; ++k) {
+      for (int k = 0; k < KC; ++k) {
         double r = e[k] * iz;
         corr += r * __builtin_amdgcn_rcp(r + kEpsMass);
         rm = fmax(rm, r);
       }
-#pragma unroll
-      for (int off = 1; off < LP; off <<= 1) {
-        corr += __shfl_xor(corr, off, 64);
-        rm = fmax(rm, __shfl_xor(rm, off, 64));
-      }
       H = log(Z) - sxe * iz - kEpsMass * corr;
       uint32_t key = (uint32_t)a.n_bins;
-      if (valid && sub == 0) {
+      if (valid) {
         // bucket slot: arrival order only (re-ranked by point index by k_bucket_rank, or by the bin
         // kernel's staging for the direct buckets)
         const uint32_t sl = atomicAdd(a.counts + nearest, 1u);
@@ -488,22 +447,21 @@ void k_points(PointKernelArgs a, double* partials) {
           // redone from k_points with members == nullptr), so they are not written here
           if (sl < (uint32_t)a.capb) a.members[(size_t)nearest * a.capb + sl] = (uint32_t)i;
           else *a.overflow = 1u;  // vector store to host-mapped memory; gcs_scan redoes the scan sorted
-          if (!GCS_PROBE_NOFLAGS && sl == 0u) {  // first arrival: mark the candidate bins and their tiles
+          if (sl == 0u) {  // first arrival: mark the candidate bins and their tiles
             // (storing each tile flag once per row measured 20 us slower at C3: the compare chain)
             const int ts = a.tile_shift;
             uint8_t* tf = a.flags + a.n_bins;
 #pragma unroll
             for (int k = 0; k < KC; ++k) {
-              const int c = LP == 1 ? cand[k % KL] : a.knn[(size_t)nearest * KC + k];
-              a.flags[c] = 1;
-              tf[c >> ts] = 1;
+              a.flags[cand[k]] = 1;
+              tf[cand[k] >> ts] = 1;
             }
           }
         } else {
           a.slots[i] = sl;
         }
       }
-      if (live && sub == 0 && !a.members) a.keys[i] = key;
+      if (live && !a.members) a.keys[i] = key;
       Z = iz;
     } else {
       for (int b = 0; b < a.n_bins; ++b) {
@@ -544,7 +502,7 @@ void k_points(PointKernelArgs a, double* partials) {
       mass_scale = s_mass[1];
       mass_in = s_mass[0];
     }
-    if (!live || sub != 0) continue;
+    if (!live) continue;
     const double wb = w_raw * mass_scale;
     const double wout = wb * win;
     if (a.t_out) a.t_out[i] = t;
@@ -581,7 +539,7 @@ void k_points(PointKernelArgs a, double* partials) {
 }
 
 // ---------------------------------------------------------------- row 1+3+5, scale mode: the lean point kernel
-// The same per-point arithmetic as k_points<true, KC, 1> (bitwise the same records, buckets, flags
+// The same per-point arithmetic as k_points<true, KC> (bitwise the same records, buckets, flags
 // and partial rows), laid out for occupancy and for the XCDs' L2s:
 //  * registers: the budget rows are folded into two doubles as soon as they land, the nearest-bin
 //    batch loads x, y, z only (24 B per id), the candidate directions arrive in groups of CG and the
@@ -593,39 +551,18 @@ void k_points(PointKernelArgs a, double* partials) {
 //    takes one contiguous eighth of the scan (an azimuth sector), and the atlas rows that sector
 //    touches (cube-cell pools, bin directions, kNN rows) are fetched into one L2 instead of all
 //    eight.  Partial rows are stored at the logical block index: the fold order is unchanged.
-#ifndef GCS_PROBE_NOEXP
-#define GCS_PROBE_NOEXP 0
-#endif
-#ifndef GCS_PROBE_NOMASS
-#define GCS_PROBE_NOMASS 0  // timing probe (not a parity build): the bin kernel's blocks skip the mass-row loads
-#endif
-#ifndef GCS_PROBE_NOFIN
-#define GCS_PROBE_NOFIN 0  // timing probe (not a parity build): phase D skips finalize_bin / the MF term
-#endif
-#ifndef GCS_LEAN_CG
-#define GCS_LEAN_CG 8  // candidate direction loads in flight per group
-#endif
-#ifndef GCS_LEAN_XCD
-#define GCS_LEAN_XCD 1  // XCD-aware block order (0: identity, for A/B)
-#endif
-#ifndef GCS_LEAN_EG
-#define GCS_LEAN_EG 4  // candidate exps interleaved per group (registers)
-#endif
-// WIDE: grids of at most one wave per SIMD (cap <= 256 CUs x 4 SIMDs x 64 lanes, C2): occupancy is
-// one wave per SIMD whatever the registers, so the 128-register target is dropped and the candidate
-// directions go out in one group (one dependent memory round trip fewer on the point's chain).
-template <int KC, bool WIDE>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WIDE ? 1 : 4)))
+template <int KC>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4)))
 void k_points_lean(PointKernelArgs a, double* partials) {
   // one point per thread (the grid covers cap: points_blocks); no grid-stride loop, so nothing
   // loop-invariant is hoisted into registers across the point's chain
-  constexpr int CG = (WIDE || KC < GCS_LEAN_CG) ? KC : GCS_LEAN_CG;
+  constexpr int CG = KC < 8 ? KC : 8;  // candidate direction loads in flight per group
+  constexpr int EG = 4;                // candidate exps interleaved per group (registers)
   static_assert(KC % CG == 0, "candidate groups");
   __shared__ double lds[kWaves * 5];
   __shared__ double s_mass[2];
   const int nb = (int)gridDim.x;
-  const int lb = (!GCS_LEAN_XCD || (nb & 7)) ? (int)blockIdx.x
-                                             : (int)(blockIdx.x & 7u) * (nb >> 3) + (int)(blockIdx.x >> 3);
+  const int lb = (nb & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7u) * (nb >> 3) + (int)(blockIdx.x >> 3);
   static_assert(kBlock * 4 >= 1024, "k_budget launches at most 1024 blocks: four rows per thread");
   double2 brow[4];
 #pragma unroll
@@ -753,7 +690,7 @@ void k_points_lean(PointKernelArgs a, double* partials) {
     e[k] = exp(x);
     Z += e[k];
     sxe += x * e[k];
-    if ((k & (GCS_LEAN_EG - 1)) == GCS_LEAN_EG - 1) __builtin_amdgcn_sched_barrier(0);  // bound the exps in flight
+    if ((k & (EG - 1)) == EG - 1) __builtin_amdgcn_sched_barrier(0);  // bound the exps in flight
   }
   const double iz = 1.0 / Z;
   double corr = 0.0, rm = 0.0;
@@ -1032,21 +969,10 @@ __device__ __forceinline__ void finalize_bin(const double* r, double* __restrict
   sc[7] = q[4] * invN - pb[2] * pb[1];
   sc[8] = q[5] * invN - pb[2] * pb[2];
   double sig[9];
-#if GCS_PROBE_NOFIN == 3  // timing probe: no PSD / kappa (the stores stay)
-  double delta = 0.0;
-  for (int k = 0; k < 9; ++k) sig[k] = sc[k];
-  double kap = r[1];
-#else
   double delta = psd_project3(sc, sig);
   double sn = sqrt(dot3_exact(r[1], r[2], r[3], r[1], r[2], r[3]));
   double kap = kappa_from_rbar(sn * invN);
-#endif
   size_t Bs = (size_t)B;
-#if GCS_PROBE_NOFIN == 2  // timing probe: the arithmetic without the 26 row stores
-  if (delta == 12345.0) scan[b] = kap + sig[4];
-  if (r[0] == 12345.0)
-#endif
-  {
   scan[SF_N * Bs + b] = N;
   scan[(SF_SD + 0) * Bs + b] = r[1];
   scan[(SF_SD + 1) * Bs + b] = r[2];
@@ -1060,7 +986,6 @@ __device__ __forceinline__ void finalize_bin(const double* r, double* __restrict
 #pragma unroll
   for (int k = 0; k < 9; ++k) scan[(SF_SIG + k) * Bs + b] = sig[k];
   scan[SF_KAPPA * Bs + b] = kap;
-  }
   cert[0] += N;
   cert[1] += N * N;
   cert[2] += N * rcp_fast(N + kEpsMass);
@@ -1125,11 +1050,7 @@ __device__ void mf_finish(const double* v, double* scalars) {
   scalars[SC_MF_NEFF] = v[9];
   scalars[SC_MF_SCANN] = v[10];
   double R[9];
-#if GCS_PROBE_NOPOLAR  // timing probe (not a parity build): R = I
-  for (int k = 0; k < 9; ++k) R[k] = k % 4 == 0 ? 1.0 : 0.0;
-#else
   mf_rotation(v, R);
-#endif
   for (int k = 0; k < 9; ++k) scalars[SC_MF_R + k] = R[k];
 }
 
@@ -1170,41 +1091,16 @@ constexpr int kBinNV = 16;
 // for B = 1k .. 1M have at most 199) and 1280 reverse-kNN entries (~K x 64; at most 1070)
 __host__ __device__ constexpr int max_src(int tb) { return 5 * tb; }
 __host__ __device__ constexpr int max_rl(int tb) { return 20 * tb; }
-#ifndef GCS_STAGE_BIG
-#define GCS_STAGE_BIG 512  // 480 (four workgroups per CU in LDS instead of three) measured slower at C2: 27.2 -> 30.5 us
-#endif
-constexpr int kStageBig = GCS_STAGE_BIG, kStageSmall = 256;
+// 480 (four workgroups per CU in LDS instead of three) measured slower at C2: 27.2 -> 30.5 us
+constexpr int kStageBig = 512, kStageSmall = 256;
 // record stages of the wider tiles (LDS per workgroup: tables + stage x 64 B)
-#ifndef GCS_STAGE_128_BIG
-#define GCS_STAGE_128_BIG 768
-#endif
-#ifndef GCS_STAGE_128_SMALL
-#define GCS_STAGE_128_SMALL 320
-#endif
-#ifndef GCS_STAGE_256_BIG
-#define GCS_STAGE_256_BIG 1024
-#endif
-#ifndef GCS_STAGE_256_SMALL
-#define GCS_STAGE_256_SMALL 640
-#endif
-#ifndef GCS_DALL64
-#define GCS_DALL64 false  // 64-bin tiles: phase D on wave 0 (every wave measured slower in round 1)
-#endif
-#ifndef GCS_DALL128
-#define GCS_DALL128 false  // 128-bin tiles: phase D on waves 0-1, one lane per bin (true: on every wave)
-#endif
-constexpr int kStage128Big = GCS_STAGE_128_BIG, kStage128Small = GCS_STAGE_128_SMALL;
-constexpr int kStage256Big = GCS_STAGE_256_BIG, kStage256Small = GCS_STAGE_256_SMALL;
-// staged record: x y z dx dy dz m w/Z as four double2 chunks (+ GCS_REC_PAD doubles of stride
-// padding); GCS_REC_SWZ stores chunk c of record r at slot c ^ ((r >> 2) & 3) (LDS bank spread)
-#ifndef GCS_REC_PAD
-#define GCS_REC_PAD 0
-#endif
-#ifndef GCS_REC_SWZ
-#define GCS_REC_SWZ 1  // A/B at C2: 33.0 -> 31.0 us; C3 unchanged (LDS conflicts are ~1/3 of LDS cycles)
-#endif
-constexpr int kRecD = 8 + GCS_REC_PAD;
-__device__ __forceinline__ uint32_t rec_swz(uint32_t r) { return GCS_REC_SWZ ? ((r >> 2) & 3u) : 0u; }
+constexpr int kStage128Big = 768, kStage128Small = 320;
+constexpr int kStage256Big = 1024, kStage256Small = 640;
+// staged record: x y z dx dy dz m w/Z as four double2 chunks; chunk c of record r is stored at
+// slot c ^ ((r >> 2) & 3) (LDS bank spread).  A/B of the swizzle at C2: 33.0 -> 31.0 us; C3
+// unchanged (LDS conflicts are ~1/3 of LDS cycles)
+constexpr int kRecD = 8;
+__device__ __forceinline__ uint32_t rec_swz(uint32_t r) { return (r >> 2) & 3u; }
 int bins_max_tile_sources(int tile_bins) { return max_src(tile_bins); }
 int bins_max_tile_entries(int tile_bins) { return max_rl(tile_bins); }
 
@@ -1227,11 +1123,7 @@ __device__ __forceinline__ void bin_contrib(double* acc, const double3& bd, doub
   double p[3] = {px, py, pz};
   double sim = dot3_exact(dx, dy, dz, bd.x, bd.y, bd.z);
   // w r = w exp((s - m)/tau) / Z   (binning.py:69 softmax, :159-160 weighting)
-#if GCS_PROBE_NOEXP  // timing probe (not a parity build): the exp's share of the gather
-  add_contrib(acc, wz * fmax(1.0 + (sim - m) * inv_tau, 1e-3), d, p);
-#else
   add_contrib(acc, wz * exp((sim - m) * inv_tau), d, p);
-#endif
 }
 
 #ifdef GCS_PHASE_PROF
@@ -1268,38 +1160,11 @@ __device__ __forceinline__ void wave_reduce_bin_terms(double (&v)[kBinNV]) {
     }
 }
 
-#ifndef GCS_RANK_LANES
-#define GCS_RANK_LANES 4  // phase A's per-bin work sum + source compaction: 4 lanes per bin (1: wave 0 alone)
-#endif
-#ifndef GCS_UNSTAGED_IDX
-#define GCS_UNSTAGED_IDX 1  // direct buckets, tile over its record stage: stage point indices (phase B)
-#endif
-#ifndef GCS_GATHER_PIPE
-// phase C: 1 loads the next staged record while accumulating the current one; 2 takes two
-// records per trip (two independent exp chains in flight)
-#define GCS_GATHER_PIPE 2
-#endif
-#ifndef GCS_STAGE_SERIAL
-#define GCS_STAGE_SERIAL 1  // phase B expands its staged 32-B records one after another (register peak)
-#endif
-#ifndef GCS_MAPV_EARLY
-#define GCS_MAPV_EARLY 1  // phase D's map direction stats are loaded before phase A
-#endif
-#ifndef GCS_BINS_WAVES
-#define GCS_BINS_WAVES 0  // waves per SIMD the register allocation targets (0: compiler default)
-#endif
-#ifndef GCS_BINS_WAVES_SMALL
-// the small-stage instantiation (C3: 25 KiB of LDS, six workgroups per CU by LDS) is register-bound:
-// 5 waves per SIMD needs <= 96 VGPRs (the register allocator spills ~28 dwords to reach it)
-#define GCS_BINS_WAVES_SMALL 0
-#endif
-#ifndef GCS_GATHER_BAL
-// phase C's lanes (tiles finalized by the first waves, !DALL): bin tiles of at least GCS_GATHER_BAL bins
+// phase C's lanes (tiles finalized by the first waves, !DALL): bin tiles of at least kGatherBal bins
 // give each bin of a wave a lane group sized by its records (balanced), smaller ones the fixed LANES
 // lanes per bin of rounds 1-4.  Same box, alternated (profiles/r05/bal/): C3 (128-bin tiles) bins
-// 84.6-85.3 -> 82.3-82.7 us; C2 (64-bin tiles) 26.9 -> 28.5-28.9 us, so 128 (0: never).
-#define GCS_GATHER_BAL 128
-#endif
+// 84.6-85.3 -> 82.3-82.7 us; C2 (64-bin tiles) 26.9 -> 28.5-28.9 us, so 128.
+constexpr int kGatherBal = 128;
 // Balanced phase-C lanes.  Wave wid gathers the bins [wid BW, wid BW + BW) (BW = 64 / LANES, the fixed
 // partition of rounds 1-4), but the 64 lanes are dealt by work: with W records and nz non-empty bins
 // in the wave and c = ceil(W / (64 - nz)), bin b gets cnt_b = ceil(w_b / c) contiguous lanes (sum <= 64:
@@ -1440,16 +1305,11 @@ __device__ __forceinline__ double mass_scale_of(const double2* s_mw, double* m_i
 // DALL: phase D on every wave -- the first lane of each bin's lane group finalizes the bin from its
 // registers right after the lanes' xor tree (no LDS hand-off, no idle waves); required for tiles
 // wider than one wave (TB > 64).  !DALL: wave 0 alone, one lane per bin (the 64-bin tile's form).
-// SPLIT (sparse maps, 128-bin tiles): phases 0 and A-C only -- each active bin's 19 raw sums go to a.raw
-// and k_bins_finalize runs phase D one thread per bin at full occupancy (the two-wave serial phase D held
-// the tile's workgroup, its LDS and its registers; the gather's register peak is lower without it).
-template <int STAGE, int TB, int LANES, bool DALL, bool SPLIT = false>
+// No register target: the compiler's default allocation (for the small-stage instantiation -- C3,
+// 25 KiB of LDS, six workgroups per CU by LDS, register-bound -- 5 waves per SIMD needs <= 96 VGPRs
+// and the register allocator spills ~28 dwords to reach it).
+template <int STAGE, int TB, int LANES, bool DALL>
 __global__ __launch_bounds__(TB * LANES)
-#if GCS_BINS_WAVES
-__attribute__((amdgpu_waves_per_eu(GCS_BINS_WAVES)))
-#elif GCS_BINS_WAVES_SMALL
-__attribute__((amdgpu_waves_per_eu(STAGE == kStageSmall ? GCS_BINS_WAVES_SMALL : 1)))
-#endif
 void k_bins_scale(BinKernelArgs a, double* partials) {
   constexpr int NT = TB * LANES, NW = NT / 64;
   constexpr int kMaxSrc = max_src(TB), kMaxRl = max_rl(TB);
@@ -1458,19 +1318,12 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
   static_assert(DALL || STAGE * kRecD >= 19 * TB, "phase D reuses the record stage for the bin sums");
   __shared__ uint32_t s_cnt[kMaxSrc], s_off[kMaxSrc], s_st[kMaxSrc];
   __shared__ double s_rec[STAGE * kRecD];
-#if GCS_RANK_LANES == 4
   // the raw reverse-kNN list is dead once phase A has compacted it, before phase B stages the
   // records: it lives in the record stage (2.5 KiB less LDS per workgroup)
   static_assert(kMaxRl * sizeof(uint16_t) <= STAGE * kRecD * sizeof(double), "raw list fits the stage");
   uint16_t* const s_rl = reinterpret_cast<uint16_t*>(s_rec);
   __shared__ uint16_t s_rlc[kMaxRl];  // each bin's non-empty sources, compacted (phase C's list)
   __shared__ uint8_t s_act[TB];
-  uint16_t* const rlist = s_rlc;
-#else
-  static_assert(!DALL, "the wave-0 work sum assumes TB <= 64");
-  __shared__ uint16_t s_rl[kMaxRl];
-  uint16_t* const rlist = s_rl;
-#endif
   __shared__ double4 s_bd[TB];
   __shared__ int s_q[TB + 1];
   __shared__ uint32_t s_work[TB];
@@ -1560,15 +1413,13 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
   const bool act_t = t < nb && a.flags[b0 + t];  // bin b0 + t (the phase-A rank's table)
   const bool own_act = DALL ? own && a.flags[b0 + own_b] : act_t;
   MapDir mapv{0.0, 0.0, 0.0, 0.0};
-  if (GCS_MAPV_EARLY && !SPLIT && own_act) mapv = load_map_dir(a.map, a.n_bins, b0 + own_b);
+  if (own_act) mapv = load_map_dir(a.map, a.n_bins, b0 + own_b);
   // phase A
   if (t < nb) s_bd[t] = *(const double4*)(a.bin_dirs + 4 * (size_t)(b0 + t));
   if (t < 3) s_org[t] = a.origin[t];
   if (t < nb) s_q[t] = q_t;
   if (t == 0) s_q[nb] = q1t;
-#if GCS_RANK_LANES == 4
   if (t < TB) s_act[t] = act_t ? 1 : 0;
-#endif
   {
     // fixed trip counts: every thread issues all of its table loads before the first LDS write,
     // so the reverse-kNN entries (up to kMaxRl / NT per thread) cost one round trip, not one each,
@@ -1580,7 +1431,7 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
     for (int k = 0; k < 4; ++k) {
       const int r = t + k * NT;
       const bool ok = a.mass_rows && r < a.mass_nrows;
-      mw[k] = ok ? (GCS_PROBE_NOMASS ? make_double2(1.0, 1.0) : a.mass_rows[r]) : make_double2(0.0, 0.0);
+      mw[k] = ok ? a.mass_rows[r] : make_double2(0.0, 0.0);
     }
     uint16_t rl[RL];
 #pragma unroll
@@ -1616,7 +1467,6 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
   __syncthreads();
   PROF(1);
   if (a.mass_rows && t == 0) s_msc = mass_scale_of<NW>(s_mw);  // (read after the next barrier)
-#if GCS_RANK_LANES == 4
   {
     // Records each bin visits (0: inactive / out of range), on the bin's four phase-C lanes: lane l
     // takes the l-th quarter of the bin's reverse-kNN entries; the non-empty sources are written,
@@ -1662,34 +1512,6 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
     for (int off = 1; off < LANES; off <<= 1) w += (uint32_t)__shfl_xor((int)w, off, 64);
     if (rq == 0) s_work[rb] = w;
   }
-#else
-  if (t < TB) {  // wave 0, lane = bin: records each bin visits (0: inactive / out of range)
-    // The bin's reverse-kNN sources are compacted in place to the non-empty ones (same order):
-    // most sources of a bin are empty buckets, and phase C's cursor then never walks them (each
-    // visit was two dependent LDS reads).  Entries are read four at a time ahead of the writes
-    // (a write never passes a read: e <= q).
-    uint32_t w = 0;
-    int e = s_q[t] - q0;
-    if (own_act) {
-      const int qa = s_q[t] - q0, qb = s_q[t + 1] - q0;
-      for (int q = qa; q < qb; q += 4) {
-        uint16_t j[4];
-        uint32_t c[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) j[u] = q + u < qb ? s_rl[q + u] : (uint16_t)0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) c[u] = q + u < qb ? s_cnt[j[u]] : 0u;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (c[u]) {
-            s_rl[e++] = j[u];
-            w += c[u];
-          }
-      }
-    }
-    s_work[t] = w;
-  }
-#endif
   const int chunk = (ns + NT - 1) / NT;
   const int j0 = min(ns, t * chunk), j1 = min(ns, j0 + chunk);
   uint32_t mine = 0;
@@ -1788,10 +1610,9 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
         d[2 ^ sw] = make_double2(dd[1], dd[2]);
         d[3 ^ sw] = make_double2(m, pr[k].w);
       }
-      if (GCS_STAGE_SERIAL) __builtin_amdgcn_sched_barrier(0);  // one record's expansion at a time (registers)
+      __builtin_amdgcn_sched_barrier(0);  // one record's expansion at a time (registers)
     }
   }
-#if GCS_UNSTAGED_IDX
   // a tile over its record stage with direct buckets: stage the records' point indices instead (4 B
   // each, in the stage's memory), ranked by point index within each source as above, so phase C
   // gathers records from L2 without re-ranking members per record
@@ -1815,15 +1636,12 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
       s_idx[s_off[lo] + rank] = me;
     }
   }
-#else
-  constexpr bool idx_staged = false;
-#endif
   __syncthreads();
   PROF(3);
   // phase C: four lanes per bin; the bin's records (sources in order, points in order) are one
   // flattened list and lane l takes the l-th quarter, so every lane's trip count is its own share
   // (no per-source max over the wave's lanes).
-  constexpr bool BAL = GCS_GATHER_BAL && TB >= GCS_GATHER_BAL && !DALL;
+  constexpr bool BAL = TB >= kGatherBal && !DALL;
   int lb, l, seg_j = 0, seg_n = 0, seg_max = 1;
   uint32_t i0, i1;
   if constexpr (BAL) {
@@ -1845,32 +1663,16 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
     // cursor: source q (local j), record k within it
     int q = s_q[lb];
     uint32_t skip = i0;
-    int j = rlist[q - q0];
+    int j = s_rlc[q - q0];
     uint32_t c = s_cnt[j];
     while (skip >= c) {
       skip -= c;
       ++q;
-      j = rlist[q - q0];
+      j = s_rlc[q - q0];
       c = s_cnt[j];
     }
     uint32_t kk = skip;
-    if (staged && !GCS_GATHER_PIPE) {
-      uint32_t r = s_off[j] + kk, left = c - kk;
-      for (uint32_t i = i0; i < i1; ++i) {
-        const double2* rp = (const double2*)(s_rec + (size_t)r * kRecD);
-        const uint32_t sw = rec_swz(r);
-        const double2 c0 = rp[0 ^ sw], c1 = rp[1 ^ sw], c2 = rp[2 ^ sw], c3 = rp[3 ^ sw];
-        bin_contrib(acc, bd, inv_tau, c0.x, c0.y, c1.x, c1.y, c2.x, c2.y, c3.x, c3.y);
-        if (--left == 0 && i + 1 < i1) {  // next source (compacted: non-empty)
-          ++q;
-          j = rlist[q - q0];
-          left = s_cnt[j];
-          r = s_off[j];
-        } else {
-          ++r;
-        }
-      }
-    } else if (staged && GCS_GATHER_PIPE == 2) {
+    if (staged) {
       // two records per trip: both records' dot / exp chains are independent, so they issue
       // interleaved (the exp chain, not the loads, is the gather's latency); the sums still take
       // record i before record i + 1, so the accumulation order is the one-record loop's
@@ -1880,7 +1682,7 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
         const uint32_t ra = r;
         if (--left == 0) {  // next source (compacted: non-empty); record i + 1 exists
           ++q;
-          j = rlist[q - q0];
+          j = s_rlc[q - q0];
           left = s_cnt[j];
           r = s_off[j];
         } else {
@@ -1890,7 +1692,7 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
         if (i + 2 < i1) {
           if (--left == 0) {
             ++q;
-            j = rlist[q - q0];
+            j = s_rlc[q - q0];
             left = s_cnt[j];
             r = s_off[j];
           } else {
@@ -1919,31 +1721,6 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
         const double2 c0 = rp[0 ^ sw], c1 = rp[1 ^ sw], c2 = rp[2 ^ sw], c3 = rp[3 ^ sw];
         bin_contrib(acc, bd, inv_tau, c0.x, c0.y, c1.x, c1.y, c2.x, c2.y, c3.x, c3.y);
       }
-    } else if (staged) {
-      // a source's records are one contiguous LDS run: the record index advances by one and is
-      // re-based only at source boundaries, and the next record is loaded (double2 x 4) while the
-      // current one is accumulated
-      uint32_t r = s_off[j] + kk, left = c - kk;
-      const double2* rp = (const double2*)(s_rec + (size_t)r * kRecD);
-      uint32_t sw = rec_swz(r);
-      double2 x0 = rp[0 ^ sw], x1 = rp[1 ^ sw], x2 = rp[2 ^ sw], x3 = rp[3 ^ sw];
-      for (uint32_t i = i0; i < i1; ++i) {
-        const double2 c0 = x0, c1 = x1, c2 = x2, c3 = x3;
-        if (i + 1 < i1) {
-          if (--left == 0) {  // next source (compacted: non-empty)
-            ++q;
-            j = rlist[q - q0];
-            left = s_cnt[j];
-            r = s_off[j];
-          } else {
-            ++r;
-          }
-          const double2* np = (const double2*)(s_rec + (size_t)r * kRecD);
-          sw = rec_swz(r);
-          x0 = np[0 ^ sw]; x1 = np[1 ^ sw]; x2 = np[2 ^ sw]; x3 = np[3 ^ sw];
-        }
-        bin_contrib(acc, bd, inv_tau, c0.x, c0.y, c1.x, c1.y, c2.x, c2.y, c3.x, c3.y);
-      }
     } else {
       for (uint32_t i = i0; i < i1; ++i) {
         uint32_t pidx;
@@ -1970,7 +1747,7 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
         if (++kk == c && i + 1 < i1) {  // next source (compacted: non-empty)
           kk = 0;
           ++q;
-          j = rlist[q - q0];
+          j = s_rlc[q - q0];
           c = s_cnt[j];
         }
       }
@@ -1990,19 +1767,6 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
       for (int off = 1; off < LANES; off <<= 1) acc[f] += __shfl_xor(acc[f], off, 64);
   }
   PROF(4);
-  if constexpr (SPLIT) {
-    // the bin's raw sums for k_bins_finalize: the lane group's first lane (a bin without records has no
-    // group and is not active: the finalize takes exact zeros for it, as phase D does)
-    static_assert(BAL && !DALL, "the split gather is the balanced 128-bin form");
-    if (seg_n > 0 && seg_j == 0) {
-      const size_t Bs = (size_t)a.n_bins, b = (size_t)(b0 + lb);
-#pragma unroll
-      for (int f = 0; f < 19; ++f) a.raw[f * Bs + b] = acc[f];
-    }
-    PROF(6);
-    PROFV(7, 1);
-    return;
-  }
   if constexpr (DALL) {
     // phase D on every wave: the group's first lane finalizes its bin from the summed registers
     double v[kBinNV];
@@ -2011,7 +1775,6 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
     v[4] = -INFINITY;
     if (own) {
       finalize_bin(acc, a.scan, a.n_bins, b0 + own_b, v);
-      if (!GCS_MAPV_EARLY && own_act) mapv = load_map_dir(a.map, a.n_bins, b0 + own_b);
       if (own_act) mf_bin_term(acc[0], acc[1], acc[2], acc[3], mapv, v + 5);
     }
     PROF(5);
@@ -2052,13 +1815,12 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
 #pragma unroll
   for (int f = 0; f < kBinNV; ++f) v[f] = 0.0;
   v[4] = -INFINITY;
-  if (own && GCS_PROBE_NOFIN != 1) {
+  if (own) {
     const bool has = !BAL || s_work[t] != 0u;  // a bin without records: exact-zero sums
 #pragma unroll
     for (int f = 0; f < 19; ++f) acc[f] = has ? s_rec[f * TB + t] : 0.0;
     finalize_bin(acc, a.scan, a.n_bins, b0 + t, v);
     PROF(15);
-    if (!GCS_MAPV_EARLY && own_act) mapv = load_map_dir(a.map, a.n_bins, b0 + t);
     if (own_act) mf_bin_term(acc[0], acc[1], acc[2], acc[3], mapv, v + 5);
   }
   PROF(5);
@@ -2078,52 +1840,6 @@ void k_bins_scale(BinKernelArgs a, double* partials) {
   }
   PROF(6);
   PROFV(7, 1);
-}
-
-// Phase D of the split bin path, one thread per bin of a tile (TB threads, one tile per workgroup): the
-// active tiles' bins (tile flag) from k_bins_scale<..., SPLIT>'s raw sums -- finalize (PSD, kappa, the 26
-// ScanBinStats rows), the Matrix-Fisher term of active bins, and the tile's partial row in the order of
-// the fused kernel's phase D (a fixed xor tree per 64-bin wave, the waves in order): the same bits.
-// Inactive tiles were finished by the gather kernel (zero-bin rows, closed-form partial row).
-template <int TB>
-__global__ __launch_bounds__(TB) void k_bins_finalize(BinKernelArgs a, double* partials) {
-  static_assert(TB % 64 == 0, "whole waves");
-  __shared__ double lds[(TB / 64) * 16];
-  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-  const int tile = (int)blockIdx.x;
-  if (!a.flags[a.n_bins + tile]) return;  // block-uniform
-  const int b0 = tile * TB, nb = min(TB, a.n_bins - b0);
-  const bool own = t < nb;
-  const bool act = own && a.flags[b0 + t];
-  const size_t Bs = (size_t)a.n_bins;
-  double acc[19];
-  MapDir mapv{0.0, 0.0, 0.0, 0.0};
-  if (act) {
-    mapv = load_map_dir(a.map, a.n_bins, b0 + t);
-#pragma unroll
-    for (int f = 0; f < 19; ++f) acc[f] = a.raw[f * Bs + b0 + t];
-  } else {
-#pragma unroll
-    for (int f = 0; f < 19; ++f) acc[f] = 0.0;
-  }
-  double v[kBinNV];
-#pragma unroll
-  for (int f = 0; f < kBinNV; ++f) v[f] = 0.0;
-  v[4] = -INFINITY;
-  if (own) {
-    finalize_bin(acc, a.scan, a.n_bins, b0 + t, v);
-    if (act) mf_bin_term(acc[0], acc[1], acc[2], acc[3], mapv, v + 5);
-  }
-  wave_reduce_bin_terms(v);
-  if (lane == 0)
-#pragma unroll
-    for (int f = 0; f < kBinNV; ++f) lds[wid * 16 + f] = v[f];
-  __syncthreads();
-  if (t < kBinNV) {
-    double x = lds[t];
-    for (int w = 1; w < TB / 64; ++w) x = t == 4 ? fmax(x, lds[w * 16 + t]) : x + lds[w * 16 + t];
-    partials[(size_t)tile * pstride<kBinNV>() + t] = x;  // folded by k_final<FIN_BINS>
-  }
 }
 
 // ---------------------------------------------------------------- row 5+6 dense mode (B small)
@@ -2362,14 +2078,7 @@ __device__ __forceinline__ void map_totals_partial(double (&tot)[kTotNV], double
 // (touched = 0: all-zero stats) stays exactly zero under forgetting + push, and its derived stats
 // keep the zero-bin constants: it is skipped (adds exact zeros to the totals).  act == nullptr
 // (dense mode): every bin is updated.
-#ifndef GCS_PUSH_WAVES
-#define GCS_PUSH_WAVES 0  // register target (waves per SIMD) of k_pushforward; 0: compiler default
-#endif
-__global__ __launch_bounds__(kBlock)
-#if GCS_PUSH_WAVES
-__attribute__((amdgpu_waves_per_eu(GCS_PUSH_WAVES)))
-#endif
-void k_pushforward(const double* __restrict__ scan, double* __restrict__ map,
+__global__ __launch_bounds__(kBlock) void k_pushforward(const double* __restrict__ scan, double* __restrict__ map,
                                                         double* __restrict__ derived, int B, PushArgs pa,
                                                         double* __restrict__ partials,
                                                         const uint8_t* __restrict__ act, uint8_t* __restrict__ touched) {
@@ -2519,13 +2228,13 @@ __global__ __launch_bounds__(kBlock) void k_map_derive(const double* __restrict_
 // mir.mirror (may be null): after the epilogue the whole scalar block, the device error words, the
 // scan's sequence number and a checksum go to the pinned host mirror (gcs_layout.h Mirror), so the
 // host reads the scan's results without a separate D2H copy and never consumes a torn mirror.
-template <int NV, unsigned MAXMASK, int KIND, int NT = kBlock>
-__global__ __launch_bounds__(NT) void k_final(const double* __restrict__ partials, int nblocks, double* scalars,
-                                              MirrorArgs mir) {
-  static_assert(NT >= MIR_SEQ, "one mirror word per thread");
-  __shared__ double lds[(NT / 64) * pstride<NV>()];
+template <int NV, unsigned MAXMASK, int KIND>
+__global__ __launch_bounds__(kBlock) void k_final(const double* __restrict__ partials, int nblocks, double* scalars,
+                                                  MirrorArgs mir) {
+  static_assert(kBlock >= MIR_SEQ, "one mirror word per thread");
+  __shared__ double lds[kWaves * pstride<NV>()];
   double v[NV];
-  reduce_partials<NV, MAXMASK, NT>(partials, nblocks, v, lds);
+  reduce_partials<NV, MAXMASK>(partials, nblocks, v, lds);
   if (threadIdx.x == 0) final_epilogue<NV, KIND>(v, scalars);
   if (mir.mirror) {
     __syncthreads();  // thread 0's epilogue stores before every thread's loads (one workgroup)
@@ -2549,7 +2258,7 @@ __global__ __launch_bounds__(NT) void k_final(const double* __restrict__ partial
     __syncthreads();
     uint64_t sum = 0;
     if (i == 0) {
-      for (int k = 0; k < NT / 64; ++k) sum += lh[k];
+      for (int k = 0; k < kWaves; ++k) sum += lh[k];
       sum += mirror_word_hash(mir.seq, MIR_SEQ);
     }
     if (mir.torn) {  // test knob: the sequence word and checksum first, the data torn microseconds later
@@ -2581,12 +2290,8 @@ __global__ __launch_bounds__(NT) void k_final(const double* __restrict__ partial
 // bin kernel at C3 took 30 us; with a first level on 128 CUs the one-block tail folds 128 rows.
 constexpr int kFoldRows = 64;
 constexpr int kFoldDirect = 2048;  // up to this many rows a single block folds directly (C2 bins: 1563)
-#ifndef GCS_FINAL_WIDE
-// threads of a direct fold over more than kFinalWideRows rows (kBlock: off).  Same-box rocprof at C2
-// (1,563 rows, profiles/r02/foldab/): 1024 threads 9.9 us, 256 threads 7.8 us -> off
-#define GCS_FINAL_WIDE 256
-#endif
-constexpr int kFinalWide = GCS_FINAL_WIDE, kFinalWideRows = 512;
+// (a direct fold always runs kBlock threads.  Same-box rocprof at C2, 1,563 rows,
+// profiles/r02/foldab/: 1024 threads 9.9 us, 256 threads 7.8 us)
 template <int NV, unsigned MAXMASK>
 __global__ __launch_bounds__(kBlock) void k_fold(const double* __restrict__ partials, int nblocks, double* out) {
   __shared__ double lds[kWaves * pstride<NV>()];
@@ -2608,9 +2313,6 @@ void launch_fold(const double* partials, int nblk, hipStream_t s, hipEvent_t e1,
     hipExtLaunchKernelGGL(k_fold<NV, MAXMASK>, dim3(g), dim3(kBlock), 0, s, e0, nullptr, 0, partials, nblk, lvl);
     hipExtLaunchKernelGGL(k_final<NV, MAXMASK, KIND>, dim3(1), dim3(kBlock), 0, s, nullptr, e1, 0,
                           (const double*)lvl, g, scalars, mirror);
-  } else if (kFinalWide != kBlock && nblk > kFinalWideRows) {  // C2 bins: 1563 rows in one or two round trips
-    hipExtLaunchKernelGGL((k_final<NV, MAXMASK, KIND, kFinalWide>), dim3(1), dim3(kFinalWide), 0, s, e0, e1, 0,
-                          partials, nblk, scalars, mirror);
   } else {
     hipExtLaunchKernelGGL(k_final<NV, MAXMASK, KIND>, dim3(1), dim3(kBlock), 0, s, e0, e1, 0, partials, nblk,
                           scalars, mirror);
@@ -2830,12 +2532,7 @@ hipError_t launch_tile_order_variant(const uint8_t* active, const uint32_t* work
   return hipGetLastError();
 }
 hipError_t launch_tile_order(const uint8_t* active, const uint32_t* work, int n, int* order, hipStream_t s) {
-  // GCSLAM_TILE_XCD=0: the round-3 order (classes only), for A/B
-  static const bool xcd = [] {
-    const char* e = getenv("GCSLAM_TILE_XCD");
-    return !(e && atoi(e) == 0);
-  }();
-  return launch_tile_order_variant(active, work, n, order, xcd, s);
+  return launch_tile_order_variant(active, work, n, order, true, s);
 }
 
 // ---------------------------------------------------------------- launchers
@@ -2848,14 +2545,8 @@ static int grid_for(long n, int cap_blocks) {
 // the 4,096-block grid took every CU's registers (256 VGPRs, two waves per SIMD) for its whole
 // length, so the next scan's budget and point kernels, which overlap it, waited for its blocks to
 // drain.  Same box, alternated (profiles/r04/pushb/): C3 0.2201 vs 0.2392-0.2396 ms per step, the
-// pushforward itself 56.8 vs 65.5-66.1 us; 256 / 512 blocks 0.2249-0.2275 ms.  GCSLAM_PUSH_BLOCKS for A/B.
-int push_blocks(int n_bins) {
-  static const int cap = [] {
-    const char* e = getenv("GCSLAM_PUSH_BLOCKS");
-    return e ? std::max(1, std::min(4096, atoi(e))) : 1024;
-  }();
-  return grid_for(n_bins, cap);
-}
+// pushforward itself 56.8 vs 65.5-66.1 us; 256 / 512 blocks 0.2249-0.2275 ms.
+int push_blocks(int n_bins) { return grid_for(n_bins, 1024); }
 
 hipError_t launch_parse(const ParseArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
@@ -2949,15 +2640,10 @@ hipError_t launch_gate(const uint64_t* gate, uint64_t seq, double* xi_out, uint3
   return hipGetLastError();
 }
 
-#ifndef GCS_POINT_LANES
-#define GCS_POINT_LANES 1  // lanes per point (scale mode); 2 and 4 measured slower, DESIGN.md section 5
-#endif
-constexpr int kPointLanes = GCS_POINT_LANES;
 constexpr int kPointsMaxBlocks = 4096;
 int points_max_blocks() { return kPointsMaxBlocks; }
 int points_blocks(long cap, bool scale) {
-  const long lanes = scale ? kPointLanes : 1;
-  const long need = (cap * lanes + kBlock - 1) / kBlock;
+  const long need = (cap + kBlock - 1) / kBlock;
   return (int)std::max(1L, std::min((long)(scale ? kPointsMaxBlocks : 1024), need));
 }
 
@@ -2966,41 +2652,27 @@ hipError_t launch_points(const PointKernelArgs& a, bool scale, double* partials,
   // without the fold (it rides in k_bins_scale's block 0) the stage ends with k_points itself
   hipEvent_t ek = fold ? nullptr : e1;
   // legacy: the round-3 point kernel (one wave per SIMD; GCSLAM_POINTS=legacy / GCS_DEBUG_POINT_KERNEL), for A/B
-  if (scale && !legacy && kPointLanes == 1 && (long)nblk * kBlock >= (long)a.cap) {  // one point per thread
-    // at most one wave per SIMD: the wide form (all 16 candidate directions in one load group, one
-    // wave per SIMD) measured slower than the 4-wave form on the same grid -- C2 points 19.8-19.9 vs
-    // 18.9 us (profiles/r04/rcp/) -- so it is opt-in (GCSLAM_POINTS_WIDE=1), kept for A/B
-    static const bool wide_ok = [] {
-      const char* e = getenv("GCSLAM_POINTS_WIDE");
-      return e && atoi(e) != 0;
-    }();
-    const bool wide = wide_ok && (long)nblk * kBlock <= 1024L * 64;
+  if (scale && !legacy && (long)nblk * kBlock >= (long)a.cap) {  // one point per thread
+    // (on grids of at most one wave per SIMD a wide form -- all 16 candidate directions in one load
+    // group, one wave per SIMD -- measured slower than this 4-wave form: C2 points 19.8-19.9 vs
+    // 18.9 us, profiles/r04/rcp/)
     switch (a.k) {
-      case 8:
-        if (wide) hipExtLaunchKernelGGL((k_points_lean<8, true>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
-        else hipExtLaunchKernelGGL((k_points_lean<8, false>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
-        break;
-      case 16:
-        if (wide) hipExtLaunchKernelGGL((k_points_lean<16, true>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
-        else hipExtLaunchKernelGGL((k_points_lean<16, false>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
-        break;
-      case 32:
-        if (wide) hipExtLaunchKernelGGL((k_points_lean<32, true>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
-        else hipExtLaunchKernelGGL((k_points_lean<32, false>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
-        break;
+      case 8: hipExtLaunchKernelGGL(k_points_lean<8>, dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials); break;
+      case 16: hipExtLaunchKernelGGL(k_points_lean<16>, dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials); break;
+      case 32: hipExtLaunchKernelGGL(k_points_lean<32>, dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials); break;
       default: return hipErrorInvalidValue;
     }
   } else if (scale) {
     switch (a.k) {
-      case 8: hipExtLaunchKernelGGL((k_points<true, 8, kPointLanes>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials); break;
-      case 16: hipExtLaunchKernelGGL((k_points<true, 16, kPointLanes>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials); break;
-      case 32: hipExtLaunchKernelGGL((k_points<true, 32, kPointLanes>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials); break;
+      case 8: hipExtLaunchKernelGGL((k_points<true, 8>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials); break;
+      case 16: hipExtLaunchKernelGGL((k_points<true, 16>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials); break;
+      case 32: hipExtLaunchKernelGGL((k_points<true, 32>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials); break;
       default: return hipErrorInvalidValue;
     }
   } else if (a.n_bins == 0) {  // deskew only (gcs_scan_begin)
-    hipExtLaunchKernelGGL((k_points<false, 0, 1>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
+    hipExtLaunchKernelGGL((k_points<false, 0>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
   } else {
-    hipExtLaunchKernelGGL((k_points<false, 1, 1>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
+    hipExtLaunchKernelGGL((k_points<false, 1>), dim3(nblk), dim3(kBlock), 0, s, e0, ek, 0, a, partials);
   }
   if (fold) GCS_FINAL_M(5, 16u, FIN_POINTS, nblk, s, e1, partials, a.scalars, mir);
   return hipGetLastError();
@@ -3037,25 +2709,24 @@ hipError_t launch_bins_scale(const BinKernelArgs& a, double* partials, hipStream
                              hipEvent_t f0, hipEvent_t f1) {
   const int nblk = bins_scale_blocks(a.n_bins, a.tile_bins);
   const bool big = (long)a.cap * 5 >= (long)a.n_bins * 2;  // C2-like: dense in the map
+  // DALL (the last template argument): the 64-bin tiles run phase D on wave 0 (every wave measured
+  // slower in round 1), the 128-bin tiles on waves 0-1, one lane per bin; the 256-bin tiles, one
+  // lane per bin in phase C already, finalize on every wave
   if (a.tile_bins == 32)  // half the records of a 64-bin tile: the small stage holds them
     hipExtLaunchKernelGGL((k_bins_scale<kStageSmall, 32, 8, false>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
   else if (a.tile_bins == 128 && big)
-    hipExtLaunchKernelGGL((k_bins_scale<kStage128Big, 128, 2, GCS_DALL128>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
-  else if (a.tile_bins == 128 && a.raw) {  // split: the gather, then phase D one thread per bin (e0 .. e1: both)
-    hipExtLaunchKernelGGL((k_bins_scale<kStage128Small, 128, 2, false, true>), dim3(nblk), dim3(256), 0, s, e0, nullptr, 0, a,
-                          partials);
-    hipExtLaunchKernelGGL(k_bins_finalize<128>, dim3(nblk), dim3(128), 0, s, nullptr, e1, 0, a, partials);
-  } else if (a.tile_bins == 128)
-    hipExtLaunchKernelGGL((k_bins_scale<kStage128Small, 128, 2, GCS_DALL128>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
+    hipExtLaunchKernelGGL((k_bins_scale<kStage128Big, 128, 2, false>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
+  else if (a.tile_bins == 128)
+    hipExtLaunchKernelGGL((k_bins_scale<kStage128Small, 128, 2, false>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
   else if (a.tile_bins == 256 && big)
     hipExtLaunchKernelGGL((k_bins_scale<kStage256Big, 256, 1, true>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
   else if (a.tile_bins == 256)
     hipExtLaunchKernelGGL((k_bins_scale<kStage256Small, 256, 1, true>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
   // (eight lanes per bin on the 64-bin tile, 512 threads: 35.2 vs 25.4 us at C2, same box)
   else if (big)
-    hipExtLaunchKernelGGL((k_bins_scale<kStageBig, 64, 4, GCS_DALL64>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
+    hipExtLaunchKernelGGL((k_bins_scale<kStageBig, 64, 4, false>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
   else
-    hipExtLaunchKernelGGL((k_bins_scale<kStageSmall, 64, 4, GCS_DALL64>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
+    hipExtLaunchKernelGGL((k_bins_scale<kStageSmall, 64, 4, false>), dim3(nblk), dim3(256), 0, s, e0, e1, 0, a, partials);
   launch_fold<kBinNV, 16u, FIN_BINS>(partials, nblk, s, f1, a.scalars, MirrorArgs{}, f0);
   return hipGetLastError();
 }
