@@ -277,15 +277,41 @@ def association_cert(o, config: AssociationConfig, N: int, chart_id: str = CHART
 _associators = {}
 
 
+ASSOC_ROW_SLOTS = 16384  # kShCR * kShThreads (gcs_assoc.hip:87): the Sinkhorn workgroup's K_mat registers
+ASSOC_MAX_K = 32         # gcs_assoc_ctx_create's max_k bound (gcs_assoc.hip:2560)
+
+
+def assoc_row_capacity(k: int) -> int:
+    """Rows one call may hold at k_assoc = k: ASSOC_ROW_SLOTS // KM with the kernels' template width
+    KM = 8, 16, 32 for k <= 8, <= 16, <= 32 (max_rows_for, gcs_assoc.hip:2491): 2,048, 1,024, 512."""
+    k = int(k)
+    if k < 1 or k > ASSOC_MAX_K:
+        raise ValueError(f"k_assoc = {k} outside [1, {ASSOC_MAX_K}]")
+    return ASSOC_ROW_SLOTS // (8 if k <= 8 else (16 if k <= 16 else 32))
+
+
+def default_context_sizes(n: int, pool: int, k: int):
+    """(max_meas, max_pool, max_k) of the drop-in function's context for a call of n rows, pool view
+    entries and k_assoc = k: the reference sizes (1,536 rows, 7 x 1,024 entries) where the width's row
+    capacity allows them, the call's own where it is larger, max_k the template width (every k of the
+    width reuses the context).  A call past the row capacity is a ValueError that names the limit."""
+    n, pool, k = int(n), int(pool), int(k)
+    limit = assoc_row_capacity(k)
+    if n < 1 or n > limit:
+        raise ValueError(f"n_total = {n} outside [1, {limit}]: the row capacity at k_assoc = {k} is {limit} "
+                         f"({ASSOC_ROW_SLOTS} // {ASSOC_ROW_SLOTS // limit})")
+    return max(n, min(1536, limit)), max(pool, 7 * 1024), ASSOC_ROW_SLOTS // limit
+
+
 def _associator_for(n, pool, k, device):
     key = device
     a = _associators.get(key)
     if a is None or a.max_meas < n or a.max_pool < pool or a.max_k < k:
+        max_meas, max_pool, max_k = default_context_sizes(n, pool, k)  # raises before the old context goes
         if a is not None:
             a.close()
-        mk = max(k, 8)
-        a = Associator(max_meas=max(n, 1536 if mk <= 8 else 1024), max_pool=max(pool, 7 * 1024), max_k=mk,
-                       device=device)
+            del _associators[key]
+        a = Associator(max_meas=max_meas, max_pool=max_pool, max_k=max_k, device=device)
         _associators[key] = a
     return a
 

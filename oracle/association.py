@@ -183,9 +183,11 @@ def stencil(cfg):
     return [(q, r, z) for z in dzs for (q, r) in disk]
 
 
-def associate_primitives_ot(batch, view, cfg=None, eps_lift=GC_EPS_LIFT, eps_mass=GC_EPS_MASS):
+def associate_primitives_ot(batch, view, cfg=None, eps_lift=GC_EPS_LIFT, eps_mass=GC_EPS_MASS, debug=None):
     """primitive_association.py:239-553.  batch: dict Lambdas (N,3,3), thetas, etas (N,L,3), weights,
-    valid_mask, n_valid; view: extract_atlas_map_view's dict.  Returns (result dict, cert dict)."""
+    valid_mask, n_valid; view: extract_atlas_map_view's dict.  Returns (result dict, cert dict).
+    debug: a dict that receives the pool of the non-empty case (cost_pool and pool_valid (N, S m),
+    has (N, S), order (N, S m)) for the tests' guards; the results do not depend on it."""
     cfg = cfg or AssociationConfig()
     K = int(cfg.k_assoc)
     valid = np.asarray(batch["valid_mask"]).astype(np.float64)
@@ -218,6 +220,8 @@ def associate_primitives_ot(batch, view, cfg=None, eps_lift=GC_EPS_LIFT, eps_mas
     pool_valid = np.asarray(view["valid_mask"])[pool_idx] & np.repeat(has[:, :, None], m, axis=2).reshape(N, -1)
     cost_pool = np.where(pool_valid, cost_pool, COST_INVALID)
     order = np.argsort(cost_pool, axis=1, kind="stable")  # lax.sort, num_keys=1, stable (:376)
+    if debug is not None:
+        debug.update(cost_pool=cost_pool, pool_valid=pool_valid, has=has, order=order)
     cand = np.take_along_axis(pool_idx, order, axis=1)[:, :K].astype(np.int32)
     cand = np.where(valid[:, None] > 0.0, cand, 0).astype(np.int32)
     slots = np.asarray(view["candidate_slots"])[cand].astype(np.int64)

@@ -107,6 +107,44 @@ def test_assoc_ctx_argument_checks(lib):
     assert lib.gcs_assoc_ctx_create(4096, 16, 8, 0, C.byref(h)) == -1    # past the one-workgroup Sinkhorn
 
 
+def _ctx_create_accepts(max_meas, max_pool, max_k):
+    """gcs_assoc_ctx_create's argument check (gcs_assoc.hip:2560) with max_rows_for (:2491) and
+    kShCR * kShThreads = 16 * 1024 (:87) restated."""
+    max_rows = 16 * 1024 // (8 if max_k <= 8 else (16 if max_k <= 16 else 32))
+    return not (max_meas < 1 or max_pool < 1 or max_k < 1 or max_k > 32 or max_meas > max_rows)
+
+
+def test_default_context_sizes_within_the_row_capacity():
+    """The drop-in function's context sizing (gcslam.association.default_context_sizes): for every
+    k_assoc and n in {1, limit, limit + 1} it gives sizes that gcs_assoc_ctx_create accepts and that
+    hold the call, or raises the ValueError that names the limit."""
+    from gcslam import association as GA
+    for k in range(1, 33):
+        limit = 16384 // (8 if k <= 8 else (16 if k <= 16 else 32))
+        assert GA.assoc_row_capacity(k) == limit
+        for pool in (1, 7 * 1024, 100000):
+            for n in (1, limit):
+                max_meas, max_pool, max_k = GA.default_context_sizes(n, pool, k)
+                assert _ctx_create_accepts(max_meas, max_pool, max_k), (n, pool, k)
+                assert max_meas >= n and max_pool >= pool and max_k >= k
+            with pytest.raises(ValueError, match=str(limit)):
+                GA.default_context_sizes(limit + 1, pool, k)
+    for k in (0, 33):
+        with pytest.raises(ValueError):
+            GA.default_context_sizes(1, 1, k)
+
+
+def test_default_context_sizes_pass_the_library_check(lib):
+    """The restated check is the library's: at the limit the largest context's size arguments pass
+    gcs_assoc_ctx_create's argument check only up to max_rows_for (a refusal there is -1 before any
+    allocation; one row past the limit is refused)."""
+    import ctypes as C
+    h = C.c_void_p()
+    for k in (8, 16, 32):
+        assert lib.gcs_assoc_ctx_create(16384 // k + 1, 16, k, 0, C.byref(h)) == -1
+        assert not _ctx_create_accepts(16384 // k + 1, 16, k) and _ctx_create_accepts(16384 // k, 16, k)
+
+
 def test_short_log_exp_pow_accuracy(lib):
     """The Sinkhorn's short log / exp (fdlibm reductions + minimax polynomials, gcs_math.h): within
     1 ulp of numpy's over the scalings' range, and x^y within 12 ulps of numpy's pow there."""

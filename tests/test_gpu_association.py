@@ -56,9 +56,9 @@ def _gcfg(c: OA.AssociationConfig) -> GA.AssociationConfig:
 _VIEW_VALID = [None]
 
 
-def _run_both(batch, view, cfg):
+def _run_both(batch, view, cfg, debug=None):
     _VIEW_VALID[0] = np.asarray(view["valid_mask"]).astype(bool)
-    ref, rc = OA.associate_primitives_ot(batch, view, cfg)
+    ref, rc = OA.associate_primitives_ot(batch, view, cfg, debug=debug)
     res, cert, eff = GA.associate_primitives_ot(_batch(batch), _view(view), _gcfg(cfg))
     torch.cuda.synchronize()
     return ref, rc, res, cert, eff
