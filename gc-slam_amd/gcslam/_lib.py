@@ -162,6 +162,29 @@ class GcsCamsplatOutputs(C.Structure):
                [("n_camera_valid", C.c_int32)]
 
 
+class GcsRenderConfig(C.Structure):
+    _fields_ = [("tile_size", C.c_int32), ("max_splats_per_tile", C.c_int32), ("fbm_octaves", C.c_int32),
+                ("fbm_gain", C.c_double), ("opacity_gamma", C.c_double), ("logdet0", C.c_double), ("eps", C.c_double),
+                ("ewa_log_clip", C.c_double), ("alpha_min", C.c_double), ("vmf_intensity_scale", C.c_double),
+                ("vmf_intensity_max", C.c_double), ("vmf_kappa_max", C.c_double), ("device", C.c_int32)]
+
+
+GCS_RENDER_MAX_VIEWS, GCS_RENDER_MAX_CAP = 32, 1024
+RENDER_ROW_FIELDS = ("positions", "covariances", "directions", "kappas", "colors", "valid_mask", "intensity")
+RENDER_VIEW_FIELDS = ("P_pix", "offsets", "view_dirs")
+RENDER_SPLAT_FIELDS = ("means", "Sigmas_inv", "radii", "alphas", "colors", "fbm")
+
+
+class GcsRenderPrepareInputs(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("n_views", C.c_int32)] + \
+               [(n, C.c_void_p) for n in RENDER_ROW_FIELDS + RENDER_VIEW_FIELDS] + \
+               [("fbm_modulate_scale", C.c_double), ("fbm_seed", C.c_int64)]
+
+
+class GcsRenderSplats(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RENDER_SPLAT_FIELDS]
+
+
 GCS_ASSOC_CERT_LEN = 21
 ASSOC_CERT_FIELDS = ("marginal_defect_a", "marginal_defect_b", "transport_mass_total", "sum_a", "sum_b", "sum_m",
                      "sum_novel", "p95_a", "p95_b", "nonzero_a", "nonzero_b", "b_recency_p95", "ess_total",
@@ -374,6 +397,19 @@ _SIGS = [
     ("gcs_camsplat_last_error", C.c_char_p, [C.c_void_p]),
     ("gcs_camsplat_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("gcs_camera_splats", C.c_int, [C.c_void_p, C.POINTER(GcsCamsplatInputs), C.POINTER(GcsCamsplatOutputs)]),
+    ("gcs_render_config_defaults", C.c_int, [C.POINTER(GcsRenderConfig)]),
+    ("gcs_render_ctx_create", C.c_int, [C.POINTER(GcsRenderConfig), C.POINTER(C.c_void_p)]),
+    ("gcs_render_ctx_destroy", C.c_int, [C.c_void_p]),
+    ("gcs_render_last_error", C.c_char_p, [C.c_void_p]),
+    ("gcs_render_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gcs_render_prepare", C.c_int, [C.c_void_p, C.POINTER(GcsRenderPrepareInputs), C.POINTER(GcsRenderSplats)]),
+    ("gcs_render_prepare_host", C.c_int, [C.POINTER(GcsRenderConfig), C.POINTER(GcsRenderPrepareInputs),
+                                          C.POINTER(GcsRenderSplats)]),
+    ("gcs_render_bin_tiles", C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 5),
+    ("gcs_render_tiles", C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32] +
+     [C.c_void_p] * 3 + [C.c_int32, C.c_void_p]),
+    ("gcs_render_view", C.c_int, [C.c_void_p, C.POINTER(GcsRenderPrepareInputs), C.c_int32, C.c_int32,
+                                  C.POINTER(GcsRenderSplats)] + [C.c_void_p] * 3),
     ("gcs_assoc_config_defaults", C.c_int, [C.POINTER(GcsAssocConfig)]),
     ("gcs_debug_short_log_exp", C.c_int, [c_double_p, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p]),
     ("gcs_debug_tab_log_exp", C.c_int, [c_double_p, C.c_int32, c_double_p, c_double_p]),

@@ -678,6 +678,90 @@ int gcs_camsplat_ctx_set_stream(gcs_camsplat_ctx* ctx, void* stream);
  * n_camera_valid 0 -- nothing is truncated silently. */
 int gcs_camera_splats(gcs_camsplat_ctx* ctx, const gcs_camsplat_inputs* in, gcs_camsplat_outputs* out);
 
+/* ---------------------------------------------------------------- primitive path: map rendering */
+/* The reference's output side (backend/rendering.py, common/bev_pushforward.py) on the GPU, reading
+ * an AtlasMapView's rows: for every (view, row) -- one thread per row, looping over the views -- the BEV pushforward to pixels, the 2 x 2 adjugate inverse,
+ * the binning radius 2 / sqrt(max(lambda_min(Sigma^-1), eps)), opacity from log det Sigma_3D,
+ * one-lobe vMF shading and world-space fBm (gcs_render_prepare); per (view, tile) the overlapping
+ * rows ordered by (distance^2 to the tile centre, row), the first max_splats_per_tile kept
+ * (gcs_render_bin_tiles, splat_indices_for_tile :252-289); per (view, tile) the normalised EWA blend
+ * of the listed rows in list order (gcs_render_tiles, render_tile_ewa :297-355).  gcs_render_view
+ * queues all three and synchronises once.  Tiles cover the image from (0, 0) = top left; tile
+ * (ty, tx) has origin (oy, ox) = (ty, tx) * tile_size and n_ty = ceil(height / tile_size),
+ * n_tx = ceil(width / tile_size).  Calls on one context must be serialised. */
+typedef struct gcs_render_ctx gcs_render_ctx;
+#define GCS_RENDER_MAX_VIEWS 32
+#define GCS_RENDER_MAX_CAP 1024
+
+typedef struct {
+  /* SplatRenderingConfig (rendering.py:28-44), same names and defaults */
+  int32_t tile_size;             /* clamped to [1, 32] as the reference does */
+  int32_t max_splats_per_tile;   /* 1 .. GCS_RENDER_MAX_CAP */
+  int32_t fbm_octaves;           /* 0 .. 16 */
+  double fbm_gain, opacity_gamma, logdet0, eps, ewa_log_clip, alpha_min;
+  double vmf_intensity_scale, vmf_intensity_max, vmf_kappa_max;
+  int32_t device;
+} gcs_render_config;
+
+/* gcs_render_prepare's inputs.  Row arrays: device for gcs_render_prepare / gcs_render_view, host for
+ * gcs_render_prepare_host.  The per-view arrays are always host arrays. */
+typedef struct {
+  int32_t n_rows, n_views;       /* n_views <= GCS_RENDER_MAX_VIEWS */
+  const double* positions;       /* n_rows x 3 */
+  const double* covariances;     /* n_rows x 9 */
+  const double* directions;      /* n_rows x 3 (normalised here) */
+  const double* kappas;          /* n_rows */
+  const double* colors;          /* n_rows x 3 */
+  const uint8_t* valid_mask;     /* n_rows; NULL = every row valid */
+  const double* intensity;       /* n_rows; NULL = no kappa modulation */
+  const double* P_pix;           /* host, n_views x 6: the 2 x 3 map to pixels */
+  const double* offsets;         /* host, n_views x 2: mu_px = P_pix p + offset */
+  const double* view_dirs;       /* host, n_views x 3 (normalised here) */
+  double fbm_modulate_scale;     /* > 0: colours carry (1 - s) + s fBm(world xy) */
+  int64_t fbm_seed;
+} gcs_render_prepare_inputs;
+
+/* The 2-D record of every (view, row).  A row that is not valid, or whose record is not finite, has
+ * radius -inf (no tile takes it) and zeros elsewhere; so has, with fbm_modulate_scale > 0, a row with
+ * |x| or |y| >= 2^46 (the fBm lattice index has to fit an int64).  fbm may be NULL. */
+typedef struct {
+  double* means;                 /* n_views x n_rows x 2 pixels (x, y) */
+  double* Sigmas_inv;            /* n_views x n_rows x 4 */
+  double* radii;                 /* n_views x n_rows */
+  double* alphas;                /* n_rows */
+  double* colors;                /* n_views x n_rows x 3: clip(colour * shading, 0, 1), times the fBm factor */
+  double* fbm;                   /* n_rows (written when fbm_modulate_scale > 0, else zeros) */
+} gcs_render_splats;
+
+int gcs_render_config_defaults(gcs_render_config* cfg);
+int gcs_render_ctx_create(const gcs_render_config* cfg, gcs_render_ctx** out);
+int gcs_render_ctx_destroy(gcs_render_ctx* ctx);
+const char* gcs_render_last_error(const gcs_render_ctx* ctx);
+/* stream: a hipStream_t (NULL = the context's own); work on it is ordered after the caller's */
+int gcs_render_ctx_set_stream(gcs_render_ctx* ctx, void* stream);
+/* Synchronises. */
+int gcs_render_prepare(gcs_render_ctx* ctx, const gcs_render_prepare_inputs* in, gcs_render_splats* out);
+/* The same rows on the host (no device, no context): every pointer is a host array. */
+int gcs_render_prepare_host(const gcs_render_config* cfg, const gcs_render_prepare_inputs* in,
+                            gcs_render_splats* out);
+/* indices: n_views x n_ty x n_tx x max_splats_per_tile int32, padded with -1; counts: n_views x n_ty x
+ * n_tx int32.  radii NULL: computed from Sigmas_inv (n_views x n_rows x 4).  Exact and bitwise
+ * reproducible for any number of overlapping rows.  Synchronises. */
+int gcs_render_bin_tiles(gcs_render_ctx* ctx, int32_t n_views, int32_t n_rows, int32_t width, int32_t height,
+                         const double* means, const double* radii, const double* Sigmas_inv, int32_t* indices,
+                         int32_t* counts);
+/* alphas: n_rows, or n_views x n_rows with alphas_per_view != 0.  image_layout 0: out is n_views x n_ty x
+ * n_tx x tile x tile x 3 (whole tiles); 1: out is n_views x height x width x 3 (the in-image part of the
+ * edge tiles).  An index outside [0, n_rows) contributes nothing.  Synchronises. */
+int gcs_render_tiles(gcs_render_ctx* ctx, int32_t n_views, int32_t n_rows, int32_t width, int32_t height,
+                     const double* means, const double* Sigmas_inv, const double* alphas, int32_t alphas_per_view,
+                     const double* colors, const int32_t* indices, const int32_t* counts, int32_t image_layout,
+                     double* out);
+/* prepare + bin + render in one call: images n_views x height x width x 3.  splats NULL (or any of its
+ * pointers NULL): the record stays in the context's workspace.  Synchronises once. */
+int gcs_render_view(gcs_render_ctx* ctx, const gcs_render_prepare_inputs* in, int32_t width, int32_t height,
+                    gcs_render_splats* splats, int32_t* indices, int32_t* counts, double* images);
+
 /* ---------------------------------------------------------------- primitive path: OT association */
 /* associate_primitives_ot (primitive_association.py:239-553) on the GPU: per measurement the MA-hex
  * stencil pool (n_stencil x m_tile_view view entries) costed by ||x_i - x_j||^2 + beta H^2_vMF
