@@ -144,10 +144,14 @@ def rank_cpus(local_rank: int, local_world: int, allowed: list[int], sysfs: str 
     """The host CPUs rank `local_rank` (on visible GPU `local_rank`) should run on, and how they were
     chosen.  The GPU's NUMA-local CPUs this process may use are split evenly between the ranks whose
     GPUs share that CPU set (a socket serving four GPUs gives each rank a quarter of it); with no
-    topology, or no allowed CPU near the GPU, the allowed CPUs are split evenly over all local ranks."""
+    topology, no allowed CPU near the GPU, or a local rank without a visible GPU, the allowed CPUs are split
+    evenly over all local ranks."""
     allowed = sorted(allowed)
     local = gpu_local_cpus(local_rank, sysfs)
-    if local:
+    # more ranks than visible GPUs (the CPU rehearsal of an 8-rank job on a one-GPU machine): a rank without
+    # a GPU has no NUMA-local set, and its even share of the allowed CPUs would overlap the NUMA-local share
+    # of a rank that has one -- every rank takes the even split
+    if local and all(gpu_local_cpus(r, sysfs) for r in range(local_world)):
         mine = [c for c in local if c in set(allowed)]
         if mine:
             key = tuple(local)

@@ -15,63 +15,9 @@ torch = pytest.importorskip("torch")
 from oracle import surfels as OS
 from gcslam import synthetic
 from gcslam.surfels import SurfelExtractionConfig, SurfelExtractor, extract_lidar_surfels
+from surfel_util import _cfg, _compare, _run
 
 pytestmark = pytest.mark.gpu
-
-
-def _cfg(o: OS.SurfelExtractionConfig) -> SurfelExtractionConfig:
-    return SurfelExtractionConfig(**{k: getattr(o, k) for k in o.__dataclass_fields__})
-
-
-def _compare(got, ref, cfg: OS.SurfelExtractionConfig):
-    n = ref["n_valid"]
-    assert got["n_valid"] == n
-    assert np.array_equal(got["bucket"].cpu().numpy(), ref["bucket"])
-    assert np.array_equal(got["count"].cpu().numpy(), ref["count"])
-    ids = got["cell_ids"].cpu().numpy()
-    assert np.array_equal(ids[:n], ref["cell_ids"]) and np.all(ids[n:] == -1)
-    for k in ("positions", "weights", "timestamps"):
-        np.testing.assert_allclose(got[k].cpu().numpy(), ref[k], rtol=1e-9, atol=1e-12, err_msg=k)
-    cov = got["covariances"].cpu().numpy().reshape(-1, 3, 3)
-    for i in range(cfg.n_surfel):
-        sc = max(np.abs(ref["covariances"][i]).max(), 1e-300)
-        np.testing.assert_allclose(cov[i], ref["covariances"][i], rtol=1e-7, atol=1e-7 * sc)
-    # normals / kappas where the plane normal is determined
-    nrm, kap = got["normals"].cpu().numpy(), got["kappas"].cpu().numpy()
-    checked = 0
-    for s, k in enumerate(ref["cell_ids"]):
-        cnt = ref["count"][k]
-        idx = ref["bucket"][k, :cnt]
-        # eigen gap of the oracle's covariance (recomputed from the members)
-        pc = np.asarray(_PTS[0])[idx] - ref["center"]
-        w = np.asarray(_PTS[1])[idx]
-        ws = w.sum() + 1e-12
-        m = (pc * w[:, None]).sum(0) / ws
-        d = pc - m
-        cv = (d * w[:, None]).T @ d / ws + 1e-12 * np.eye(3)
-        ev = np.linalg.eigvalsh(cv)
-        if ev[1] - ev[0] > 1e-6 * ev[2]:
-            np.testing.assert_allclose(nrm[s], ref["normals"][s], rtol=0, atol=1e-7)
-            np.testing.assert_allclose(kap[s], ref["kappas"][s], rtol=1e-6)
-            checked += 1
-    return checked
-
-
-_PTS = [None, None]
-
-
-def _run(points, t, w, ocfg, device_center=True):
-    _PTS[0], _PTS[1] = points, w
-    ex = SurfelExtractor(_cfg(ocfg), max_points=max(len(points), 16))
-    try:
-        got = ex.extract(points, t, w, want_intermediates=True)
-    finally:
-        ex.close()
-    mask, w_eff, c_np = OS.point_mask_and_center(points, w, ocfg.eig_min)
-    # sums of +-metres cancel in a near-zero component: absolute bar 1e-13 of the coordinate scale
-    np.testing.assert_allclose(got["center"], c_np, rtol=1e-12, atol=1e-13 * max(np.abs(points[mask]).max(), 1.0))
-    ref = OS.extract_surfels_mahex3d(points, t, w, ocfg, center=got["center"] if device_center else None)
-    return got, ref
 
 
 def test_reference_smoke_two_clusters_on_gpu():
@@ -83,7 +29,7 @@ def test_reference_smoke_two_clusters_on_gpu():
                                      hex3d_num_cells_1=8, hex3d_num_cells_2=8, hex3d_num_cells_z=2,
                                      hex3d_max_occupants=32)
     got, ref = _run(pts, t, w, ocfg)
-    _compare(got, ref, ocfg)
+    _compare(got, ref, ocfg, pts, w)
     batch, cert, eff = extract_lidar_surfels(torch.from_numpy(pts).cuda(), torch.from_numpy(t).cuda(),
                                              torch.from_numpy(w).cuda(), config=_cfg(ocfg))
     assert batch.n_surfel == 8 and batch.n_feat == 4
@@ -112,7 +58,7 @@ def test_synthetic_scan_matches_oracle(n_points, scan):
     ocfg = OS.SurfelExtractionConfig()
     got, ref = _run(pts, sc["timestamps"], sc["weights"], ocfg)
     assert ref["n_valid"] > 100
-    checked = _compare(got, ref, ocfg)
+    checked = _compare(got, ref, ocfg, pts, sc["weights"])
     assert checked > 0.5 * ref["n_valid"]
 
 
@@ -124,7 +70,7 @@ def test_sentinels_empty_input_and_capacity():
     ocfg = OS.SurfelExtractionConfig(n_surfel=64, hex3d_num_cells_1=8, hex3d_num_cells_2=8, hex3d_num_cells_z=4,
                                      voxel_size_m=0.25)
     got, ref = _run(pts, t, w, ocfg)
-    _compare(got, ref, ocfg)
+    _compare(got, ref, ocfg, pts, w)
     assert not np.isin(np.arange(0, 300, 7), got["bucket"].cpu().numpy()).any()
     ex = SurfelExtractor(_cfg(ocfg), max_points=300)
     try:

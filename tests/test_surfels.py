@@ -89,3 +89,56 @@ def test_selection_valid_first_by_cell_id_and_padded_tail():
     assert n == min(int(ext["cell_valid"].sum()), cfg.n_surfel)
     # weights: the clusters' unit weights, split over their cells
     assert ext["weights"][:n].sum() <= 40.0 + 1e-9
+
+
+@pytest.mark.parametrize("clipped", [False, True])
+def test_only_occupied_equals_full_loop(clipped):
+    """extract_surfels_mahex3d(only_occupied=True) fits only the cells that hold a point: every returned array
+    equals the full loop's (the cell_fit rows of empty cells excluded: they are never selected)."""
+    import surfel_util as SU
+    if clipped:
+        pts, t, w = SU.ladder_scene((1, 2, 3, 9, 40), (8, 8, 2), 0.5, 3)
+        cfg = S.SurfelExtractionConfig(n_surfel=16, n_feat=4, voxel_size_m=0.5, hex3d_num_cells_1=8,
+                                       hex3d_num_cells_2=8, hex3d_num_cells_z=2, hex3d_max_occupants=8)
+    else:
+        pts, t, w = SU.grid_scene(12, 4, (5, 7, 3), 0.25, 4)
+        cfg = S.SurfelExtractionConfig(n_surfel=105, voxel_size_m=0.25, hex3d_num_cells_1=5, hex3d_num_cells_2=7,
+                                       hex3d_num_cells_z=3, hex3d_max_occupants=8)
+    full = S.extract_surfels_mahex3d(pts, t, w, cfg)
+    fast = S.extract_surfels_mahex3d(pts, t, w, cfg, only_occupied=True)
+    raw = np.bincount(full["linear"][full["mask"]], minlength=cfg.n_cells)
+    assert (raw > cfg.hex3d_max_occupants).any() == clipped and (raw == 0).any() and full["n_valid"] > 0
+    assert full.keys() == fast.keys()
+    for k in full:
+        if k == "cell_fit":
+            occ = full["count"] > 0
+            for f in full[k]:
+                assert np.array_equal(full[k][f][occ], fast[k][f][occ]), f
+        else:
+            assert np.array_equal(np.asarray(full[k]), np.asarray(fast[k])), k
+
+
+def _shape_cases():
+    import surfel_util as SU
+    return SU.CASES + [c for s in SU.SEQUENCES for c in SU.sequence_cases(s)]
+
+
+@pytest.mark.parametrize("case", _shape_cases(), ids=[c.id for c in _shape_cases()])
+def test_shape_case_guards_hold_on_the_oracle(case):
+    """Every case of tests/test_gpu_surfel_shapes.py, built and run through the oracle alone: its guards (the
+    assertions that show the case reaches its branch of gcs_surfels.hip) hold before anything runs on a GPU."""
+    import surfel_util as SU
+    SU.guards(case, case.oracle())
+
+
+def test_dispatch_restated_at_its_edges():
+    """surfel_util.dispatch at the thresholds of gcs_surfels.hip's launch code."""
+    import surfel_util as SU
+    d = SU.dispatch
+    assert [d(1, c).end_bit for c in (1, 2, 127, 128, 16383, 16384, 1 << 18, (1 << 19) - 1, 1 << 19)] == \
+        [1, 2, 7, 8, 14, 15, 19, 19, 20]
+    assert [d(1, c).npass for c in (1, 127, 128, 16383, 16384)] == [1, 1, 2, 2, 3]
+    assert [d(n, 1 << 18).sort for n in (0, 1, 8192, 8193, 16384)] == ["none", "lds13", "lds13", "rocprim", "rocprim"]
+    assert [d(n, (1 << 18) - 1).sort for n in (8192, 8193, 16384, 16385)] == ["lds13", "lds14", "lds14", "rocprim"]
+    assert d(100, 1 << 19).sort == "rocprim" and d(100, 1024, lds_sort=False).sort == "rocprim"
+    assert [d(1, c).per for c in (1, 1024, 1025, 16384, 16385, 1 << 19)] == [1, 1, 2, 16, 17, 512]

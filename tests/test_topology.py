@@ -83,3 +83,14 @@ def test_rank_cpus_without_topology_split_the_allowed_set(tmp_path, clean_env):
     cpus, how = T.rank_cpus(2, 4, list(range(8)), str(tmp_path))
     assert cpus == [4, 5] and "no topology" in how
     assert T.rank_cpus(0, 1, list(range(8)), str(tmp_path))[0] == list(range(8))
+
+
+def test_rank_cpus_with_more_ranks_than_gpus_stay_disjoint(tmp_path, clean_env):
+    """Eight ranks on a machine with one visible GPU (the CPU rehearsal of the 8-rank layout): rank 0's GPU has
+    a NUMA-local set, ranks 1-7 have no GPU; the shares must not overlap, so every rank takes the even split."""
+    root = _fake_sysfs(str(tmp_path), n_gpus=1)
+    allowed = list(range(128))
+    shares = [T.rank_cpus(r, 8, allowed, root)[0] for r in range(8)]
+    assert sum(len(s) for s in shares) == len(set().union(*map(set, shares))) == 128
+    assert shares[0] == list(range(16)) and shares[7] == list(range(112, 128))
+    assert T.rank_cpus(0, 1, allowed, root)[1].startswith("numa-local")   # one rank, one GPU: as before
