@@ -1763,7 +1763,7 @@ template <int KM>
 __global__ __launch_bounds__(kFinThreads) void k_as_finish(AsIn in, AsParams p, AsWork w, AsOut o, int n_valid_host,
                                                            const int32_t* n_valid_dev) {
   __shared__ double s_red[(kFinThreads / 64) * (7 + KM)];
-  if ((n_valid_dev ? *n_valid_dev : n_valid_host) == 0 || *w.mvalid == 0u) return;  // the Sinkhorn's empty result
+  if (n_valid_host + (n_valid_dev ? *n_valid_dev : 0) == 0 || *w.mvalid == 0u) return;  // the Sinkhorn's empty result
   finish_block<KM, kFinThreads>(in, p, w, o, blockIdx.x, gridDim.x, s_red, [] { return true; });
 }
 
@@ -1782,7 +1782,7 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int N = p.n, K = p.k;
   if (blockIdx.x == 0) SH_STAMP(0);
-  const bool empty = (n_valid_dev ? *n_valid_dev : n_valid_host) == 0 || *w.mvalid == 0u;
+  const bool empty = n_valid_host + (n_valid_dev ? *n_valid_dev : 0) == 0 || *w.mvalid == 0u;
   if (empty) {  // :272-287 -- zeros, exact cert (workgroup 0)
     if (blockIdx.x != 0) return;
     for (int q = t; q < N * K; q += kShThreads) {
@@ -2305,7 +2305,7 @@ struct VpeIn {
   const double *Lambdas, *thetas, *etas;
   const uint8_t* valid;
   int n, n_lobes, n_meas;
-  const int32_t* n_meas_dev;  // (may be null) the count on the device, read instead of n_meas
+  const int32_t* n_meas_dev;  // (may be null) a further count on the device (the LiDAR rows), added to n_meas
   const double *vpos, *vdir, *vkap;
   const uint8_t* vvalid;
   int m_view;
@@ -2388,7 +2388,7 @@ __global__ __launch_bounds__(kVpeThreads) void k_as_vpe(VpeIn in, const double* 
   double acc[kVpeVals];
   for (int q = 0; q < kVpeVals; ++q) acc[q] = 0.0;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int n_meas = in.n_meas_dev ? max(0, *in.n_meas_dev) : in.n_meas;
+  const int n_meas = in.n_meas + (in.n_meas_dev ? max(0, *in.n_meas_dev) : 0);
   int base = 0;  // valid rows before this chunk
   for (int c0 = 0; c0 < in.n; c0 += kVpeThreads) {
     const int i = c0 + threadIdx.x;
@@ -2750,10 +2750,11 @@ int assoc_launch(gcs_assoc_ctx* c, const gcs_assoc_config* cfg, const gcs_assoc_
   };
   if (bad_policy) {
     uint32_t mvh = 0;
-    int32_t nvh = m->n_valid;
+    int32_t nvh = 0;
     ASCHK(c, hipMemcpyAsync(&mvh, mv, 4, hipMemcpyDeviceToHost, s));
     if (n_valid_dev) ASCHK(c, hipMemcpyAsync(&nvh, n_valid_dev, 4, hipMemcpyDeviceToHost, s));
     ASCHK(c, hipStreamSynchronize(s));
+    nvh += m->n_valid;
     if (nvh != 0 && mvh != 0) return as_fail(c, GCS_ERR_ARG, bad_policy);  // rearm zeroes the next counter
     // empty: the Sinkhorn kernel's zero path writes the reference's empty result
   }

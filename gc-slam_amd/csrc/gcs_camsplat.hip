@@ -5,7 +5,8 @@
 //
 //   k_cs_box       the query pixels' bounding box grown by the radius; clears the call's counters
 //   k_cs_count     per point: p_cam = R^T (p - t), z > 0, pixel (u, v) (:80-96, :123); per block the
-//                  count of points in front of the camera and of those inside the box
+//                  count of points in front of the camera and of those inside the box; the points are an
+//                  n x 3 f64 array or the scan's own records (CsPts: float32 widened exactly, same bits)
 //   k_cs_offsets   one workgroup: exclusive scan of the block counts
 //   k_cs_compact   the projected table (u, v, x, y, z of the kept points), stable in point order
 //   k_cs_feature   one workgroup per feature: candidates within the radius into LDS in point order
@@ -26,6 +27,7 @@
 #include <algorithm>
 #include <string>
 
+#include "gcs_live.h"
 #include "gcs_math.h"
 #include "gcslam_hip.h"
 
@@ -65,10 +67,27 @@ struct CsOut {
 // counters of one call (device): [0] table entries, [1] points with z > 0, [2] first overflowing feature
 constexpr int kCntTab = 0, kCntPos = 1, kCntErr = 2;
 
+// the points: records of `step` bytes with x, y, z at their start -- fmt 0: float32 at bytes 0, 4, 8 (the
+// scan's PointCloud2 records, gcs_scan_inputs.xyz_dev), widened exactly; fmt 1: float64 at bytes 0, 8, 16
+// (an n x 3 f64 array is fmt 1 with step 24)
+struct CsPts {
+  const void* base;
+  int step, fmt;
+};
+
 // p_cam = R^T (p - t) and the pixel of _project_camera (:92-94); true where z > 0
-__device__ __forceinline__ bool cs_project(const double* __restrict__ p, int i, const CsParams& a, double* pc,
-                                           double* u, double* v) {
-  const double dx = p[3 * (size_t)i] - a.t[0], dy = p[3 * (size_t)i + 1] - a.t[1], dz = p[3 * (size_t)i + 2] - a.t[2];
+__device__ __forceinline__ bool cs_project(const CsPts& s, int i, const CsParams& a, double* pc, double* u,
+                                           double* v) {
+  const char* rec = (const char*)s.base + (size_t)i * (size_t)s.step;
+  double px, py, pz;
+  if (s.fmt == 0) {
+    const float* f = (const float*)rec;
+    px = (double)f[0]; py = (double)f[1]; pz = (double)f[2];
+  } else {
+    const double* d = (const double*)rec;
+    px = d[0]; py = d[1]; pz = d[2];
+  }
+  const double dx = px - a.t[0], dy = py - a.t[1], dz = pz - a.t[2];
   pc[0] = a.R[0] * dx + a.R[3] * dy + a.R[6] * dz;
   pc[1] = a.R[1] * dx + a.R[4] * dy + a.R[7] * dz;
   pc[2] = a.R[2] * dx + a.R[5] * dy + a.R[8] * dz;
@@ -111,7 +130,7 @@ __global__ __launch_bounds__(kCsThreads) void k_cs_box(const double* __restrict_
   }
 }
 
-__global__ __launch_bounds__(kCsThreads) void k_cs_count(const double* __restrict__ p, int n, CsParams a,
+__global__ __launch_bounds__(kCsThreads) void k_cs_count(CsPts p, int n, CsParams a,
                                                           const double* __restrict__ box,
                                                           int32_t* __restrict__ blk_cnt) {
   __shared__ int s_c[kCsWaves][2];
@@ -163,7 +182,7 @@ __global__ __launch_bounds__(kCsThreads) void k_cs_offsets(const int32_t* __rest
 }
 
 // table rows: u | v | x | y | z, each a column of `cap` entries
-__global__ __launch_bounds__(kCsThreads) void k_cs_compact(const double* __restrict__ p, int n, CsParams a,
+__global__ __launch_bounds__(kCsThreads) void k_cs_compact(CsPts p, int n, CsParams a,
                                                             const double* __restrict__ box,
                                                             const int32_t* __restrict__ blk_off, double* __restrict__ tab,
                                                             int cap) {
@@ -598,13 +617,29 @@ int gcs_camsplat_ctx_set_stream(gcs_camsplat_ctx* c, void* stream) {
   return GCS_OK;
 }
 
-int gcs_camera_splats(gcs_camsplat_ctx* c, const gcs_camsplat_inputs* in, gcs_camsplat_outputs* out) {
+}  // extern "C"
+
+namespace gcs {
+namespace live {
+int camsplat_bind_stream(gcs_camsplat_ctx* c, void* s) {
+  if ((hipStream_t)s == c->stream) return GCS_OK;
+  CSCHK(c, hipSetDevice(c->device));
+  CSCHK(c, hipStreamSynchronize(c->stream));
+  c->stream = (hipStream_t)s;
+  return GCS_OK;
+}
+
+int camsplat_launch(gcs_camsplat_ctx* c, const gcs_camsplat_inputs* in, const void* xyz, int32_t point_step,
+                    int32_t xyz_format, int32_t n_points, gcs_camsplat_outputs* out, int32_t* n_valid_host) {
   if (!c || !in || !out) return GCS_ERR_ARG;
   const gcs_camsplat_config& cf = c->cfg;
-  const int n = in->n_points, m = in->n_features;
+  const int n = n_points, m = in->n_features;
   if (n < 0 || n > cf.max_points) return cs_fail(c, GCS_ERR_ARG, "n_points exceeds max_points");
   if (m < 0 || m > 65535) return cs_fail(c, GCS_ERR_ARG, "n_features out of range");
-  if (n > 0 && !in->points_base) return cs_fail(c, GCS_ERR_ARG, "null points");
+  if (n > 0 && !xyz) return cs_fail(c, GCS_ERR_ARG, "null points");
+  if (xyz_format == 0 ? (point_step < 12 || point_step % 4 != 0) : (xyz_format != 1 || point_step < 24 || point_step % 8 != 0))
+    return cs_fail(c, GCS_ERR_ARG, "xyz_format 0 needs a point_step >= 12 (a multiple of 4), xyz_format 1 one >= 24 "
+                                   "(a multiple of 8)");
   if (m > 0 && (!in->u || !in->v || !in->depth_Lambda_c || !in->depth_theta_c || !in->xyz || !in->cov ||
                 !in->weight || !in->kappa_app || !in->mu_app || !in->has_mu || !in->color || !in->has_color))
     return cs_fail(c, GCS_ERR_ARG, "null feature array");
@@ -639,16 +674,17 @@ int gcs_camera_splats(gcs_camsplat_ctx* c, const gcs_camsplat_inputs* in, gcs_ca
            out->source_indices, out->valid_mask, out->n_pt, out->z_med, out->mad, out->Lambda_A, out->theta_A,
            out->Lambda_B, out->theta_B, out->z_f, out->fused};
   const int n_valid = std::min(m, cf.n_feat);
+  const CsPts pts{xyz, point_step, xyz_format};
   hipLaunchKernelGGL(k_cs_box, dim3(1), dim3(kCsThreads), 0, s, in->u, in->v, m, a.box_margin, c->d_box, c->d_cnt);
   if (m > 0) {
     if (n > 0) {
       const int nblk = (n + kCsThreads - 1) / kCsThreads;
-      hipLaunchKernelGGL(k_cs_count, dim3(nblk), dim3(kCsThreads), 0, s, in->points_base, n, a,
-                         (const double*)c->d_box, c->d_blk_cnt);
+      hipLaunchKernelGGL(k_cs_count, dim3(nblk), dim3(kCsThreads), 0, s, pts, n, a, (const double*)c->d_box,
+                         c->d_blk_cnt);
       hipLaunchKernelGGL(k_cs_offsets, dim3(1), dim3(kCsThreads), 0, s, (const int32_t*)c->d_blk_cnt, nblk,
                          c->d_blk_off, c->d_cnt);
-      hipLaunchKernelGGL(k_cs_compact, dim3(nblk), dim3(kCsThreads), 0, s, in->points_base, n, a,
-                         (const double*)c->d_box, (const int32_t*)c->d_blk_off, c->d_tab, cf.max_points);
+      hipLaunchKernelGGL(k_cs_compact, dim3(nblk), dim3(kCsThreads), 0, s, pts, n, a, (const double*)c->d_box,
+                         (const int32_t*)c->d_blk_off, c->d_tab, cf.max_points);
     }
     hipLaunchKernelGGL(k_cs_feature, dim3(m), dim3(kCsThreads), 0, s, (const double*)c->d_tab, cf.max_points,
                        c->d_cnt, a, ci, m, co);
@@ -656,13 +692,37 @@ int gcs_camera_splats(gcs_camsplat_ctx* c, const gcs_camsplat_inputs* in, gcs_ca
   hipLaunchKernelGGL(k_cs_finish, dim3((cf.n_feat + kCsThreads - 1) / kCsThreads), dim3(kCsThreads), 0, s,
                      (const int32_t*)c->d_cnt, n_valid, cf.n_feat, co, c->h_status_dev);
   CSCHK(c, hipGetLastError());
-  CSCHK(c, hipStreamSynchronize(s));
+  if (n_valid_host) *n_valid_host = n_valid;
+  return GCS_OK;
+}
+
+// after the stream's wait: k_cs_finish's status -- n_camera_valid and the first feature over max_candidates
+int camsplat_collect(gcs_camsplat_ctx* c, gcs_camsplat_outputs* out) {
   out->n_camera_valid = c->h_status[0];
   if (c->h_status[1] != INT_MAX)
     return cs_fail(c, GCS_ERR_STATE, "feature " + std::to_string(c->h_status[1]) + " has more than max_candidates=" +
-                                         std::to_string(cf.max_candidates) +
+                                         std::to_string(c->cfg.max_candidates) +
                                          " LiDAR points within lidar_projection_radius_pix; no camera row was written");
   return GCS_OK;
+}
+}  // namespace live
+}  // namespace gcs
+
+extern "C" {
+
+int gcs_camera_splats(gcs_camsplat_ctx* c, const gcs_camsplat_inputs* in, gcs_camsplat_outputs* out) {
+  if (!c || !in || !out) return GCS_ERR_ARG;
+  if (int rc = gcs::live::camsplat_launch(c, in, in->points_base, 24, 1, in->n_points, out, nullptr)) return rc;
+  CSCHK(c, hipStreamSynchronize(c->stream));
+  return gcs::live::camsplat_collect(c, out);
+}
+
+int gcs_camera_splats_scan(gcs_camsplat_ctx* c, const gcs_camsplat_inputs* in, const void* xyz_dev, int32_t point_step,
+                           int32_t xyz_format, int32_t n_points, gcs_camsplat_outputs* out) {
+  if (!c || !in || !out) return GCS_ERR_ARG;
+  if (int rc = gcs::live::camsplat_launch(c, in, xyz_dev, point_step, xyz_format, n_points, out, nullptr)) return rc;
+  CSCHK(c, hipStreamSynchronize(c->stream));
+  return gcs::live::camsplat_collect(c, out);
 }
 
 }  // extern "C"

@@ -2553,7 +2553,27 @@ int gcs_ma_hex_stencil(const double* center3, double h_tile, int32_t radius_xy, 
 
 int gcs_live_scan(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_outputs* bo, const gcs_live_args* a,
                   gcs_live_outputs* lo, gcs_scan_outputs* out) {
+  return gcs_live_scan_camera(c, in, bo, a, nullptr, lo, out);
+}
+
+int gcs_live_scan_camera(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_outputs* bo, const gcs_live_args* a,
+                         const gcs_live_camera* cam, gcs_live_outputs* lo, gcs_scan_outputs* out) {
   if (!c || !bo || !a || !lo || !out) return fail(c, GCS_ERR_ARG, "null argument");
+  if (cam) {
+    const gcs_camsplat_outputs* o = cam->out;
+    if (!o || !o->Lambdas || !o->thetas || !o->etas || !o->weights || !o->sources || !o->source_indices ||
+        !o->valid_mask || !o->timestamps || !o->colors)
+      return fail(c, GCS_ERR_ARG, "gcs_live_scan_camera: null camera batch array");
+    if (cam->ctx ? !cam->in : !cam->src)
+      return fail(c, GCS_ERR_ARG, "gcs_live_scan_camera: form A needs in, form B needs src");
+    if (!cam->ctx) {
+      const gcs_camsplat_outputs* q = cam->src;
+      if (!q->Lambdas || !q->thetas || !q->etas || !q->weights || !q->sources || !q->source_indices ||
+          !q->valid_mask || !q->timestamps || !q->colors || cam->n_feat < 0 || cam->n_feat > a->meas.n_total ||
+          q->n_camera_valid < 0 || q->n_camera_valid > cam->n_feat)
+        return fail(c, GCS_ERR_ARG, "gcs_live_scan_camera: bad source slice");
+    }
+  }
   if (!a->surfels || !a->assoc || !a->map || !a->assoc_cfg || !a->update_cfg || !a->surfel_out || !a->view ||
       !a->view_tile_ids_dev || !a->assoc_out || !a->vpe_out || !a->lidar_sources_dev ||
       !a->assoc_out->candidate_pool_indices || !a->assoc_out->candidate_tile_ids || !a->assoc_out->candidate_slots)
@@ -2566,11 +2586,23 @@ int gcs_live_scan(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_outputs*
   const clk::time_point t_in = clk::now();
   auto mark = [&](int k) { lo->phase_us[k] = 1e3 * ms_between(t_in, clk::now()); };
   int rc;
-  if (in) {
-    if ((rc = gcs_scan_begin(c, in, bo))) return rc;
-  } else if (!c->live_pending) {
-    return fail(c, GCS_ERR_STATE, "gcs_live_scan without gcs_scan_begin");
+  if (!in && !c->live_pending) return fail(c, GCS_ERR_STATE, "gcs_live_scan without gcs_scan_begin");
+  hipStream_t s = c->stream;
+  int32_t n_cam = 0;  // the batch's camera rows, known on the host; the LiDAR rows are counted on the device
+  const bool cam_a = cam && cam->ctx;
+  if (cam_a) {
+    // form A: the camera slice from the scan's records (backend_node.py:1865-1925), queued ahead of the
+    // begin's host prologue (it reads nothing the begin writes); the batch is zeroed ahead of it
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (live::camsplat_bind_stream(cam->ctx, s))
+      return sub_fail(c, GCS_ERR_HIP, "camera splats", gcs_camsplat_last_error(cam->ctx));
+    if (a->zero_dev && a->zero_bytes > 0) HIPCHK(c, hipMemsetAsync(a->zero_dev, 0, (size_t)a->zero_bytes, s));
+    if ((rc = live::camsplat_launch(cam->ctx, cam->in, cam->xyz_dev, cam->point_step, cam->xyz_format, cam->n_points,
+                                    cam->out, &n_cam)))
+      return sub_fail(c, rc, "gcs_camera_splats", gcs_camsplat_last_error(cam->ctx));
+    mark(8);
   }
+  if (in && (rc = gcs_scan_begin(c, in, bo))) return rc;
   mark(0);
   // the scan's tiles around the predicted position (pipeline.py:783-797)
   const int na = ma_hex_stencil(bo->pose_pred, a->h_tile, a->r_active_xy, a->r_active_z, lo->active_ids,
@@ -2605,7 +2637,6 @@ int gcs_live_scan(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_outputs*
   gcs_surfel_ctx* sf = a->surfels;
   gcs_assoc_ctx* as = a->assoc;
   gcs_pmap* pm = a->map;
-  hipStream_t s = c->stream;
   if (live::surfel_bind_stream(sf, s)) return sub_fail(c, GCS_ERR_HIP, "surfels", gcs_surfel_last_error(sf));
   if (live::assoc_bind_stream(as, s)) return sub_fail(c, GCS_ERR_HIP, "association", gcs_assoc_last_error(as));
   if (live::pmap_bind_stream(pm, s)) return sub_fail(c, GCS_ERR_HIP, "map", gcs_pmap_last_error(pm));
@@ -2634,7 +2665,20 @@ int gcs_live_scan(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_outputs*
       return sub_fail(c, rc, "gcs_pmap_clear_tile", gcs_pmap_last_error(pm));
     }
   ncl = 0;
-  if (a->zero_dev && a->zero_bytes > 0) HIPCHK(c, hipMemsetAsync(a->zero_dev, 0, (size_t)a->zero_bytes, s));
+  if (!cam_a && a->zero_dev && a->zero_bytes > 0) HIPCHK(c, hipMemsetAsync(a->zero_dev, 0, (size_t)a->zero_bytes, s));
+  if (cam && !cam_a) {
+    // form B: the camera slice gcs_camera_splats built earlier, its n_feat rows copied behind the zeroing
+    const gcs_camsplat_outputs *q = cam->src, *d = cam->out;
+    const size_t nf = (size_t)cam->n_feat, lobes = (size_t)a->meas.n_lobes;
+    const struct { void* dst; const void* src; size_t row; } cp[9] = {
+        {d->Lambdas, q->Lambdas, 72}, {d->thetas, q->thetas, 24}, {d->etas, q->etas, 24 * lobes},
+        {d->weights, q->weights, 8}, {d->sources, q->sources, 4}, {d->source_indices, q->source_indices, 4},
+        {d->valid_mask, q->valid_mask, 1}, {d->timestamps, q->timestamps, 8}, {d->colors, q->colors, 24}};
+    for (const auto& e : cp)
+      if (nf > 0) HIPCHK(c, hipMemcpyAsync(e.dst, e.src, nf * e.row, hipMemcpyDeviceToDevice, s));
+    n_cam = q->n_camera_valid;
+    mark(8);
+  }
   // surfels of the deskewed points (pipeline.py:778-782), the batch's LiDAR sources set on its valid
   // rows; the launches behind them read the surfel count on the device (no host wait here)
   gcs_surfel_outputs sfo = *a->surfel_out;
@@ -2652,7 +2696,7 @@ int gcs_live_scan(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_outputs*
     return sub_fail(c, rc, "gcs_pmap_extract_view", gcs_pmap_last_error(pm));
   // OT association (:816-878)
   gcs_assoc_meas m = a->meas;
-  m.n_valid = 0;  // n_camera_valid (0: a LiDAR-only batch) + n_lidar_valid: read on the device (nv_dev)
+  m.n_valid = n_cam;  // n_camera_valid (0: a LiDAR-only batch); n_lidar_valid is added on the device (nv_dev)
   gcs_assoc_view v{};
   v.tile_ids = a->view_tile_ids_dev;
   v.n_tiles = ns;
@@ -2690,7 +2734,13 @@ int gcs_live_scan(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_outputs*
   const int nv = so->n_valid;
   live::assoc_collect(as, ao);
   live::pmap_recency_collect(pm, nrec, lo->recency_stats);
-  live::vpe_collect(as, nv, a->assoc_cfg->k_assoc, bo->z_lin_pose, a->eps_lift, vo);
+  live::vpe_collect(as, n_cam + nv, a->assoc_cfg->k_assoc, bo->z_lin_pose, a->eps_lift, vo);
+  if (cam_a) {  // k_cs_finish's status: a feature over max_candidates fails the scan here, ahead of the finish
+    if ((rc = live::camsplat_collect(cam->ctx, cam->out)))
+      return sub_fail(c, rc, "gcs_camera_splats", gcs_camsplat_last_error(cam->ctx));
+  } else if (cam) {
+    cam->out->n_camera_valid = n_cam;
+  }
   mark(4);
   // the finish: trigger magnitudes of the surfel (identity influence), recency (exact), association
   // (mass_epsilon_ratio unless exact) and visual (lift_strength = eps_lift unless exact) certs; ESS of

@@ -21,7 +21,8 @@ const int32_t* surfel_nvalid_dev(gcs_surfel_ctx* c);
 int surfel_bind_stream(gcs_surfel_ctx* c, void* s);
 
 // gcs_associate_primitives_ot (primitive_association.py:239-553)
-// n_valid_dev (may be null): the measurement count on the device, read by the kernels instead of m->n_valid
+// n_valid_dev (may be null): a further measurement count on the device (the chain's LiDAR rows); the kernels
+// use m->n_valid (the camera rows, known on the host) + *n_valid_dev
 int assoc_launch(gcs_assoc_ctx* c, const gcs_assoc_config* cfg, const gcs_assoc_meas* m, const gcs_assoc_view* v,
                  gcs_assoc_outputs* o, const int32_t* n_valid_dev = nullptr);
 void assoc_collect(gcs_assoc_ctx* c, gcs_assoc_outputs* o);
@@ -32,6 +33,15 @@ int vpe_launch(gcs_assoc_ctx* c, const gcs_assoc_meas* m, const gcs_assoc_view* 
                const double* z_lin_pose, double eps_lift, double eps_mass, const int32_t* n_valid_dev = nullptr);
 void vpe_collect(gcs_assoc_ctx* c, int32_t n_valid, int32_t k_assoc, const double* z_lin_pose, double eps_lift,
                  gcs_vpe_outputs* o);
+
+// gcs_camera_splats / gcs_camera_splats_scan (backend_node.py:1865-1925): the points as records (xyz_format 0:
+// float32 x, y, z at bytes 0, 4, 8 of point_step bytes; 1: float64, step >= 24); in->points_base / n_points
+// are not read.  n_valid_host (may be null): min(M, n_feat), known at launch.  collect reads the status
+// k_cs_finish wrote: n_camera_valid, and GCS_ERR_STATE naming the first feature over max_candidates
+int camsplat_launch(gcs_camsplat_ctx* c, const gcs_camsplat_inputs* in, const void* xyz, int32_t point_step,
+                    int32_t xyz_format, int32_t n_points, gcs_camsplat_outputs* out, int32_t* n_valid_host);
+int camsplat_collect(gcs_camsplat_ctx* c, gcs_camsplat_outputs* out);
+int camsplat_bind_stream(gcs_camsplat_ctx* c, void* s);
 
 int pmap_bind_stream(gcs_pmap* p, void* s);
 // create_empty_tile (primitive_map.py:148-174) without the wait

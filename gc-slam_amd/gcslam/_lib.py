@@ -292,6 +292,14 @@ class GcsLiveOutputs(C.Structure):
                 ("update", GcsPmapUpdateStats), ("counts", C.c_int32 * LIVE_MAX_TILES), ("next_global_id", C.c_int64)]
 
 
+class GcsLiveCamera(C.Structure):
+    # form A: ctx, inputs (a GcsCamsplatInputs), the scan's records; form B (ctx NULL): src (a GcsCamsplatOutputs),
+    # n_feat; out (a GcsCamsplatOutputs): the batch's camera slice in both
+    _fields_ = [("ctx", C.c_void_p), ("inputs", C.c_void_p), ("xyz_dev", C.c_void_p), ("point_step", C.c_int32),
+                ("xyz_format", C.c_int32), ("n_points", C.c_int32), ("src", C.c_void_p), ("n_feat", C.c_int32),
+                ("out", C.c_void_p)]
+
+
 _SIGS = [
     ("gcs_version", C.c_char_p, []),
     ("gcs_abi_version", C.c_int, []),
@@ -397,6 +405,8 @@ _SIGS = [
     ("gcs_camsplat_last_error", C.c_char_p, [C.c_void_p]),
     ("gcs_camsplat_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("gcs_camera_splats", C.c_int, [C.c_void_p, C.POINTER(GcsCamsplatInputs), C.POINTER(GcsCamsplatOutputs)]),
+    ("gcs_camera_splats_scan", C.c_int, [C.c_void_p, C.POINTER(GcsCamsplatInputs), C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_int32, C.POINTER(GcsCamsplatOutputs)]),
     ("gcs_render_config_defaults", C.c_int, [C.POINTER(GcsRenderConfig)]),
     ("gcs_render_ctx_create", C.c_int, [C.POINTER(GcsRenderConfig), C.POINTER(C.c_void_p)]),
     ("gcs_render_ctx_destroy", C.c_int, [C.c_void_p]),
@@ -450,6 +460,8 @@ _SIGS = [
     ("gcs_live_scan", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GcsScanBeginOutputs), C.POINTER(GcsLiveArgs),
                                 C.POINTER(GcsLiveOutputs), C.POINTER(GcsScanOutputs)]),
     ("gcs_live_collect", C.c_int, [C.c_void_p, C.POINTER(GcsLiveOutputs)]),
+    ("gcs_live_scan_camera", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GcsScanBeginOutputs), C.POINTER(GcsLiveArgs),
+                                       C.c_void_p, C.POINTER(GcsLiveOutputs), C.POINTER(GcsScanOutputs)]),
     ("gcs_ma_hex_stencil", C.c_int, [c_double_p, C.c_double, C.c_int32, C.c_int32, c_int64_p, C.c_int32]),
 ]
 

@@ -5,12 +5,15 @@ node does per scan between its visual feature buffer and feature_list_to_camera_
 base frame and the camera slice of the MeasurementBatch (camera_batch_utils.py,
 structures/measurement_batch.py:165-259) -- through gcs_camera_splats (libgcslam_hip.so).  The batch
 it returns goes to extract_lidar_surfels(base_batch=...) or to
-process_scan_single_hypothesis(camera_batch=..., config.camera_batch_policy="use")."""
+process_scan_single_hypothesis(camera_batch=..., config.camera_batch_policy="use").  A CameraFrame (the
+features with the camera's intrinsics and pose) goes to process_scan_single_hypothesis in the batch's
+place: the slice is then built from the scan's own points inside the one-call live scan
+(gcs_live_scan_camera)."""
 
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, fields
+from dataclasses import dataclass, field, fields
 from typing import Optional
 
 import numpy as np
@@ -156,22 +159,54 @@ class CameraSplatBuilder:
         torch = _torch()
         dev = f"cuda:{self.device}"
         fa = features if getattr(features, "_on_device", False) else self.device_features(features)
-        m = int(fa["u"].shape[0])
-        batch = create_empty_measurement_batch(self.n_feat, self.n_surfel, dev)
-        if m == 0:   # camera_batch_utils.py:35-37
-            return batch
+        if int(fa["u"].shape[0]) == 0:   # camera_batch_utils.py:35-37
+            return create_empty_measurement_batch(self.n_feat, self.n_surfel, dev)
         p = torch.as_tensor(points_base, dtype=torch.float64, device=dev).reshape(-1, 3).contiguous()
+        return self._run(fa, p, None, intrinsics, R_base_camera, t_base_camera, timestamp_sec, want_diag)
+
+    def build_from_records(self, features, xyz_dev, point_step: int, xyz_format: int, n_points: int,
+                           intrinsics: PinholeIntrinsics, R_base_camera, t_base_camera, timestamp_sec: float,
+                           want_diag: bool = False) -> MeasurementBatch:
+        """build() on the scan's own records (gcs_camera_splats_scan): xyz_dev, a device tensor holding
+        n_points records of point_step bytes -- xyz_format 0: float32 x, y, z at bytes 0, 4, 8 (what
+        gcs_scan_inputs.xyz_dev holds); 1: float64 at bytes 0, 8, 16.  Bit for bit build() on the float64
+        array of the same values."""
+        dev = f"cuda:{self.device}"
+        fa = features if getattr(features, "_on_device", False) else self.device_features(features)
+        if int(fa["u"].shape[0]) == 0:
+            return create_empty_measurement_batch(self.n_feat, self.n_surfel, dev)
+        need = (int(n_points) - 1) * int(point_step) + (24 if int(xyz_format) == 1 else 12) if n_points > 0 else 0
+        if n_points < 0 or need > xyz_dev.numel() * xyz_dev.element_size():
+            raise ValueError("xyz_dev holds fewer than n_points records")
+        return self._run(fa, xyz_dev, (int(point_step), int(xyz_format), int(n_points)), intrinsics, R_base_camera,
+                         t_base_camera, timestamp_sec, want_diag)
+
+    def inputs_struct(self, fa, intrinsics, R_base_camera, t_base_camera, timestamp_sec) -> "L.GcsCamsplatInputs":
+        """gcs_camsplat_inputs of device features fa (points_base / n_points left unset)."""
         i = L.GcsCamsplatInputs()
-        i.points_base, i.n_points = p.data_ptr(), int(p.shape[0])
         R = np.ascontiguousarray(R_base_camera, np.float64).reshape(9)
         t = np.ascontiguousarray(t_base_camera, np.float64).reshape(3)
         i.R_base_camera[:], i.t_base_camera[:] = R.tolist(), t.tolist()
         i.fx, i.fy, i.cx, i.cy = (float(getattr(intrinsics, k)) for k in ("fx", "fy", "cx", "cy"))
-        i.n_features = m
+        i.n_features = int(fa["u"].shape[0])
         for name in ("u", "v", "depth_Lambda_c", "depth_theta_c", "xyz", "cov", "weight", "kappa_app", "mu_app",
                      "has_mu", "color", "has_color"):
             setattr(i, name, fa[name].data_ptr())
         i.timestamp_sec = float(timestamp_sec)
+        return i
+
+    def diag_tensors(self, m: int) -> dict:
+        """Fresh per-feature diagnostic arrays (gcs_camsplat_outputs' optional pointers) for m features."""
+        torch = _torch()
+        dt = {"n_pt": torch.int32, "fused": torch.uint8}
+        return {k: torch.empty(m, dtype=dt.get(k, torch.float64), device=f"cuda:{self.device}")
+                for k in L.CAMSPLAT_DIAG_FIELDS}
+
+    def _run(self, fa, points, records, intrinsics, R_base_camera, t_base_camera, timestamp_sec, want_diag):
+        torch = _torch()
+        dev = f"cuda:{self.device}"
+        batch = create_empty_measurement_batch(self.n_feat, self.n_surfel, dev)
+        i = self.inputs_struct(fa, intrinsics, R_base_camera, t_base_camera, timestamp_sec)
         o = L.GcsCamsplatOutputs()
         sl = slice(0, self.n_feat)
         for name in L.CAMSPLAT_BATCH_FIELDS:
@@ -179,42 +214,149 @@ class CameraSplatBuilder:
             setattr(o, name, (x.view(torch.uint8) if name == "valid_mask" else x).data_ptr())
         diag = None
         if want_diag:
-            dt = {"n_pt": torch.int32, "fused": torch.uint8}
-            diag = {k: torch.empty(m, dtype=dt.get(k, torch.float64), device=dev) for k in L.CAMSPLAT_DIAG_FIELDS}
+            diag = self.diag_tensors(int(i.n_features))
             for k, x in diag.items():
                 setattr(o, k, x.data_ptr())
         self._chk(self.lib.gcs_camsplat_ctx_set_stream(self.h, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
                   "gcs_camsplat_ctx_set_stream")
-        self._chk(self.lib.gcs_camera_splats(self.h, C.byref(i), C.byref(o)), "gcs_camera_splats")
+        if records is None:
+            i.points_base, i.n_points = points.data_ptr(), int(points.shape[0])
+            self._chk(self.lib.gcs_camera_splats(self.h, C.byref(i), C.byref(o)), "gcs_camera_splats")
+        else:
+            step, fmt, n = records
+            self._chk(self.lib.gcs_camera_splats_scan(self.h, C.byref(i), C.c_void_p(points.data_ptr()), step, fmt, n,
+                                                      C.byref(o)), "gcs_camera_splats_scan")
         batch.n_camera_valid = int(o.n_camera_valid)
         if diag is not None:
             batch.camera_diag = diag
         return batch
 
     def device_features(self, features) -> dict:
-        """feature_arrays(features) on the builder's GPU (reusable across calls on the same features)."""
-        torch = _torch()
-        dev = f"cuda:{self.device}"
-        fa = _DeviceFeatures((k, torch.as_tensor(v, device=dev).contiguous()) for k, v in feature_arrays(features).items())
-        return fa
+        """feature_arrays(features) on the builder's GPU (reusable across calls on the same features): the
+        twelve arrays through one pinned staging buffer and one H2D copy, as the scan's points go."""
+        return _upload_features(feature_arrays(features), self.device)
 
 
 class _DeviceFeatures(dict):
     _on_device = True
 
 
+_stage = {}
+
+
+def _upload_features(fa: dict, device: int) -> "_DeviceFeatures":
+    """Host feature arrays (feature_arrays' dict) -> device tensors: one pinned staging buffer per
+    (device, stream), grown to the largest feature set seen, and one H2D copy into a fresh device buffer
+    (the f64 arrays first, 8-byte aligned, then the two uint8 flags); before the staging buffer is refilled
+    the event of its previous copy is waited on."""
+    torch = _torch()
+    dev = f"cuda:{device}"
+    m = int(fa["u"].shape[0])
+    widths = [(name, max(w, 1)) for name, w in _FEATURE_ARRAYS]
+    nbytes = (8 * m * sum(w for _, w in widths) + 2 * m + 7) // 8 * 8
+    stream = torch.cuda.current_stream(dev)
+    key = (int(device), stream.cuda_stream)
+    ent = _stage.get(key)
+    if ent is not None and ent[0].numel() < nbytes:
+        if ent[2]:
+            ent[1].synchronize()   # the last copy out of the old buffer before it is dropped
+        ent = None
+    if ent is None:
+        hb = torch.empty(-(-max(nbytes, 1 << 16) // 4096) * 4096, dtype=torch.uint8).pin_memory()
+        ent = _stage[key] = [hb, torch.cuda.Event(), False, hb.numpy()]
+    hb, ev, used, hn = ent
+    if used:
+        ev.synchronize()
+    off, spans = 0, []
+    for name, w in widths:
+        z = 8 * m * w
+        hn[off:off + z].view(np.float64)[...] = np.asarray(fa[name], np.float64).reshape(-1)
+        spans.append((name, off, z, torch.float64, (m, w) if w > 1 else (m,)))
+        off += z
+    for name in ("has_mu", "has_color"):
+        hn[off:off + m] = np.asarray(fa[name]).astype(np.uint8).reshape(-1)
+        spans.append((name, off, m, torch.uint8, (m,)))
+        off += m
+    d = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if nbytes:
+        d.copy_(hb[:nbytes], non_blocking=True)
+        ev.record(stream)
+        ent[2] = True
+    return _DeviceFeatures((name, d[o:o + z].view(dt).view(sh)) for name, o, z, dt, sh in spans)
+
+
 _builders = {}
 
 
-def _builder_for(config, n_feat, n_surfel, eps_lift, n_points, device):
-    key = (config, int(n_feat), int(n_surfel), float(eps_lift), int(device))
+def _builder_for(config, n_feat, n_surfel, eps_lift, n_points, device, max_candidates=1024):
+    key = (config, int(n_feat), int(n_surfel), float(eps_lift), int(device), int(max_candidates))
     b = _builders.get(key)
-    if b is None or b.max_points < n_points:
+    if b is None or b.h is None or b.max_points < n_points:
         if b is not None:
             b.close()
         b = _builders[key] = CameraSplatBuilder(config, n_feat=n_feat, n_surfel=n_surfel, eps_lift=eps_lift,
-                                                max_points=max(n_points, 8192), device=device)
+                                                max_points=max(n_points, 8192), max_candidates=max_candidates,
+                                                device=device)
     return b
+
+
+@dataclass
+class CameraFrame:
+    """One scan's visual features as the node holds them ahead of its hypothesis loop
+    (backend_node.py:1834-1925): the feature set (see feature_arrays), the pinhole intrinsics, the camera's
+    pose in the base frame (p_base = R p_camera + t), the batch's timestamp and the depth-fusion config.
+    process_scan_single_hypothesis(camera_batch=CameraFrame(...), camera_batch_policy="use") builds the
+    batch's camera slice from the scan's own points inside the scan (the node's splat_prep_fused reads the
+    scan's base-frame points, :1872-1884).  want_diag: result.camera_diag holds the per-feature
+    diagnostics.  max_candidates: the points within one feature's radius held at once (<= 1024); a denser
+    feature fails the scan, naming the feature."""
+    features: object
+    intrinsics: PinholeIntrinsics
+    R_base_camera: object
+    t_base_camera: object
+    timestamp_sec: float
+    config: DepthFusionConfig = field(default_factory=DepthFusionConfig)
+    want_diag: bool = False
+    max_candidates: int = 1024
+
+    def __post_init__(self):
+        if self.config is None:
+            self.config = DepthFusionConfig()
+        if not isinstance(self.config, DepthFusionConfig):
+            raise TypeError("CameraFrame.config: a DepthFusionConfig")
+        R = np.array(self.R_base_camera, np.float64)
+        t = np.array(self.t_base_camera, np.float64)
+        if R.shape != (3, 3) or not np.isfinite(R).all():
+            raise ValueError("CameraFrame.R_base_camera: a finite 3 x 3 matrix")
+        if t.reshape(-1).shape != (3,) or not np.isfinite(t).all():
+            raise ValueError("CameraFrame.t_base_camera: three finite values")
+        self.R_base_camera, self.t_base_camera = R, t.reshape(3)
+        k = [float(getattr(self.intrinsics, n)) for n in ("fx", "fy", "cx", "cy")]
+        if not np.isfinite(k).all() or k[0] <= 0.0 or k[1] <= 0.0:
+            raise ValueError("CameraFrame.intrinsics: finite fx, fy > 0, cx, cy")
+        self.timestamp_sec = float(self.timestamp_sec)
+        if not np.isfinite(self.timestamp_sec):
+            raise ValueError("CameraFrame.timestamp_sec is not finite")
+        if not 1 <= int(self.max_candidates) <= 1024:
+            raise ValueError("CameraFrame.max_candidates outside [1, 1024]")
+        self.arrays = feature_arrays(self.features)   # host arrays, validated once
+        m = self.n_features
+        if m > 65535:
+            raise ValueError("CameraFrame: more than 65535 features")
+        for name, w in _FEATURE_ARRAYS:
+            if self.arrays[name].shape != ((m, w) if w else (m,)):
+                raise ValueError(f"CameraFrame.features[{name!r}]: shape {self.arrays[name].shape}")
+
+    @property
+    def n_features(self) -> int:
+        return int(self.arrays["u"].shape[0])
+
+    @property
+    def n_valid(self) -> int:   # (an empty frame is no camera batch: the scan runs LiDAR-only)
+        return self.n_features
+
+    def builder(self, n_feat, n_surfel, eps_lift, n_points, device) -> CameraSplatBuilder:
+        return _builder_for(self.config, n_feat, n_surfel, eps_lift, n_points, device, self.max_candidates)
 
 
 def camera_batch_from_features(features, points_base, intrinsics: PinholeIntrinsics, R_base_camera, t_base_camera,

@@ -194,6 +194,7 @@ class ScanPipelineResult:
     z_lin_pose: Optional[np.ndarray] = None
     map_record: Optional[dict] = None  # the map update's inputs (primitive_map_follow)
     stage_ms: Optional[dict] = None    # live path, config.enable_timing: wall ms per stage (synced)
+    camera_diag: Optional[dict] = None  # a CameraFrame with want_diag: the per-feature depth-fusion diagnostics
 
 
 IMU_ODOM_CERTS = (("OdomEvidenceGaussian",), ("ImuAccelDirectionTimeResolved", "TransportConsistencyWeighting"),
@@ -370,18 +371,31 @@ def _process_scan_primitive(ctx: HypothesisContext, primitive_map, belief_prev, 
     preintegration, deskew, IMU/odometry branch, z_lin_pose) -> the map branch (:778-926) -> visual
     pose evidence (:980-1010) -> gcs_scan_finish (tempering, fusion, recompose, anchor drift) ->
     step 12b at z_t (:1232-1492).  camera_batch (camera_batch_policy "use"): the surfels join its camera
-    slice (extract_lidar_surfels(base_batch=...), pipeline.py:781-795); the one-call chain has no camera
-    rows, so such a scan takes the per-operator path."""
+    slice (extract_lidar_surfels(base_batch=...), pipeline.py:781-795).  A gcslam.camera.CameraFrame's
+    slice is built from the scan's own points (backend_node.py:1865-1925): inside the one-call chain, or
+    here with camera_batch_from_features when the chain is off -- the same kernels on the same values."""
     import torch
     from . import association as GA, primitive_map as GPM
+    from .camera import CameraFrame
     from .surfels import SurfelExtractionConfig, extract_lidar_surfels
-    if camera_batch is not None and (camera_batch.n_feat != config.n_feat or camera_batch.n_surfel != config.n_surfel):
+    frame = camera_batch if isinstance(camera_batch, CameraFrame) else None
+    if camera_batch is not None and frame is None and \
+            (camera_batch.n_feat != config.n_feat or camera_batch.n_surfel != config.n_surfel):
         raise ValueError(f"camera_batch budgets ({camera_batch.n_feat}, {camera_batch.n_surfel}) differ from the "
                          f"config's n_feat / n_surfel ({config.n_feat}, {config.n_surfel})")
-    if camera_batch is None and _live_chain_enabled(ctx, config):
+    if _live_chain_enabled(ctx, config):
         return _process_scan_live_chain(ctx, primitive_map, rec, t, w, imu_stamps, imu_gyro, imu_accel, odom_pose,
                                         odom_cov_se3, scan_start_time, scan_end_time, dt_sec, t_last_scan, t_scan, Q,
-                                        config, odom_twist, odom_twist_cov, scan_seq, L_ext, h_ext, update_map)
+                                        config, odom_twist, odom_twist_cov, scan_seq, L_ext, h_ext, update_map,
+                                        camera=camera_batch)
+    camera_diag = None
+    if frame is not None:
+        # the scan's own point values (the float32 records, widened exactly) through gcs_camera_splats
+        b = frame.builder(config.n_feat, config.n_surfel, config.eps_lift, int(rec.shape[0]), config.device)
+        camera_batch = b.build(b.device_features(frame.arrays), rec[:, :3].to(torch.float64), frame.intrinsics,
+                               frame.R_base_camera, frame.t_base_camera, frame.timestamp_sec,
+                               want_diag=frame.want_diag)
+        camera_diag = getattr(camera_batch, "camera_diag", None)
     cap = ctx.cfg.n_points_cap
     dev = f"cuda:{config.device}"
     bufs = getattr(ctx, "_live_bufs", None)
@@ -478,7 +492,7 @@ def _process_scan_primitive(ctx: HypothesisContext, primitive_map, belief_prev, 
                   batch=batch, association=res)
     return out, dict(map=am, batch=batch, map_update_cert=muc, certs=[c_surf, c_infl, c_assoc, c_vis],
                      association=res, view=view, visual=vis, z_lin_pose=z_lin_pose, map_record=record,
-                     stage_ms=stage_ms)
+                     stage_ms=stage_ms, camera_diag=camera_diag)
 
 
 def _live_chain_enabled(ctx: HypothesisContext, config: "PipelineConfig") -> bool:
@@ -620,11 +634,14 @@ def _arena_typed(buf) -> dict:
 
 def _process_scan_live_chain(ctx: HypothesisContext, primitive_map, rec, t, w, imu_stamps, imu_gyro, imu_accel,
                              odom_pose, odom_cov_se3, scan_start_time, scan_end_time, dt_sec, t_last_scan, t_scan, Q,
-                             config: "PipelineConfig", odom_twist, odom_twist_cov, scan_seq, L_ext, h_ext, update_map):
+                             config: "PipelineConfig", odom_twist, odom_twist_cov, scan_seq, L_ext, h_ext, update_map,
+                             camera=None):
     """_process_scan_primitive through gcs_live_scan: begin -> surfels -> recency -> view -> association ->
     visual pose evidence -> finish -> step 12b in one C call on the context's stream (pipeline.py:316-1591;
     :778-1011, 1232-1492), with this scan's fresh result tensors handed in.  Step 12b is left running:
-    live["finish"]() waits for it and fills the MapUpdateCert and the map's bookkeeping."""
+    live["finish"]() waits for it and fills the MapUpdateCert and the map's bookkeeping.  camera: a
+    CameraFrame (gcs_live_scan_camera's form A: the camera slice is built from the scan's records inside
+    the call, ahead of the begin) or a MeasurementBatch (form B: its camera slice is copied in)."""
     import torch
     from . import association as GA, primitive_map as GPM
     from .association import AtlasMapView
@@ -678,8 +695,42 @@ def _process_scan_live_chain(ctx: HypothesisContext, primitive_map, rec, t, w, i
     a.scan_seq = st["c_as"].scan_seq = int(scan_seq)
     a.timestamp = float(scan_end_time)
     out = L.GcsScanOutputs()
+    cam = cam_out = cam_diag = None
+    if camera is not None:
+        cam, cam_out = L.GcsLiveCamera(), L.GcsCamsplatOutputs()
+        for name in L.CAMSPLAT_BATCH_FIELDS:  # row 0 of the batch's own arrays
+            setattr(cam_out, name, base + lay["off"][("batch", name)])
+        cam.out = C.addressof(cam_out)
+        if hasattr(camera, "arrays"):  # a CameraFrame: form A, on the records the begin reads
+            from .camera import _upload_features
+            b = camera.builder(config.n_feat, config.n_surfel, config.eps_lift, int(rec.shape[0]), config.device)
+            fa = _upload_features(camera.arrays, config.device)
+            ci = b.inputs_struct(fa, camera.intrinsics, camera.R_base_camera, camera.t_base_camera,
+                                 camera.timestamp_sec)
+            cam.ctx, cam.inputs = b.h.value, C.addressof(ci)
+            cam.xyz_dev, cam.point_step, cam.xyz_format = inp.xyz_dev, inp.point_step, inp.xyz_format
+            cam.n_points = inp.n_points
+            if camera.want_diag:
+                cam_diag = b.diag_tensors(int(ci.n_features))
+                for k, x in cam_diag.items():
+                    setattr(cam_out, k, x.data_ptr())
+            cam_keep = (b, fa, ci)
+        else:  # a MeasurementBatch whose camera slice gcs_camera_splats filled: form B
+            src = L.GcsCamsplatOutputs()
+            cam_keep = [src]
+            for name in L.CAMSPLAT_BATCH_FIELDS:
+                x = getattr(camera, name)
+                x = x if x.is_contiguous() and x.device == buf.device else x.to(buf.device).contiguous()
+                cam_keep.append(x)
+                setattr(src, name, x.data_ptr())
+            src.n_camera_valid = int(camera.n_camera_valid)
+            cam.src, cam.n_feat = C.addressof(src), int(config.n_feat)
     _stamp("args")
-    rc = lib.gcs_live_scan(ctx.h, in_ref, C.byref(bo), C.byref(a), C.byref(lo), C.byref(out))
+    if cam is None:
+        rc = lib.gcs_live_scan(ctx.h, in_ref, C.byref(bo), C.byref(a), C.byref(lo), C.byref(out))
+    else:
+        rc = lib.gcs_live_scan_camera(ctx.h, in_ref, C.byref(bo), C.byref(a), C.byref(cam), C.byref(lo), C.byref(out))
+        del cam_keep
     _stamp("live_scan")
     del keep
     if lo.n_created:  # tiles created (and cleared where written) before the device failed or ran
@@ -688,13 +739,15 @@ def _process_scan_live_chain(ctx: HypothesisContext, primitive_map, rec, t, w, i
     try:
         typed = _arena_typed(buf)
         bt = _arena_tensors(typed, lay["batch"])
-        batch = MeasurementBatch(**bt, n_feat=config.n_feat, n_surfel=config.n_surfel, n_camera_valid=0,
+        batch = MeasurementBatch(**bt, n_feat=config.n_feat, n_surfel=config.n_surfel,
+                                 n_camera_valid=int(cam_out.n_camera_valid) if cam_out is not None else 0,
                                  n_lidar_valid=0)
         vt = _arena_tensors(typed, lay["view"])
         view_tids = vt.pop("tile_ids")
         a_out = _arena_tensors(typed, lay["assoc"])
         r = _live_chain_results(ctx, am, st, lo, o_sf, bo, out, batch, vt, view_tids, a_out, ao, scan_seq,
                                 scan_end_time, config)
+        r["camera_diag"] = cam_diag
         _stamp("live_results")
         return out, r
     except BaseException:
@@ -795,8 +848,12 @@ def process_scan_single_hypothesis(belief_prev: BeliefGaussianInfo, raw_points, 
     (default), raises, is ignored, or is used.  "use" with a primitive_map hands it to
     extract_lidar_surfels(base_batch=camera_batch) (pipeline.py:781-795): association, pose evidence
     and map update then see camera splats and LiDAR surfels together, and result.measurement_batch
-    carries both slices.  Such a scan runs operator by operator: the one-call gcs_live_scan chain has
-    no camera rows.  On the bin path (no primitive_map) nothing consumes the batch and "use" warns
+    carries both slices (n_camera_valid set).  camera_batch may also be a gcslam.camera.CameraFrame -- the
+    scan's visual features with the camera's intrinsics and pose: the camera slice is then built from
+    this scan's own points, as the node builds it ahead of its hypothesis loop (backend_node.py:1865-1925),
+    and result.camera_diag holds its diagnostics when the frame asks for them.  Both kinds go through the
+    one-call chain (gcs_live_scan_camera) when it is enabled and operator by operator otherwise, with the
+    same bits.  On the bin path (no primitive_map) nothing consumes the batch and "use" warns
     like "warn".  L_ext / h_ext add further caller evidence to step 9.
 
     primitive_map (an AtlasMap): the live primitive path (pipeline.py:778-1011, 1232-1492) replaces the
@@ -878,6 +935,7 @@ def _scan_result(ctx, out, live, belief_prev, scan_seq, scan_end_time, dt_sec, n
         res.z_lin_pose = live["z_lin_pose"]
         res.map_record = live["map_record"]
         res.stage_ms = live["stage_ms"]
+        res.camera_diag = live.get("camera_diag")
         res.map_bins_updated = None
     # the reference's per-scan MinimalScanTape (pipeline.py:1504-1570)
     res.diagnostics_tape = tape_from_result(res, scan_seq, scan_end_time, dt_sec, n_raw, res.L_evidence)

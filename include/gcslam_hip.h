@@ -677,6 +677,14 @@ int gcs_camsplat_ctx_set_stream(gcs_camsplat_ctx* ctx, void* stream);
  * (the message names the first such feature): every batch row is then zero / invalid and
  * n_camera_valid 0 -- nothing is truncated silently. */
 int gcs_camera_splats(gcs_camsplat_ctx* ctx, const gcs_camsplat_inputs* in, gcs_camsplat_outputs* out);
+/* The same on the scan's own records -- the points splat_prep_fused sees in the node are the scan's
+ * base-frame points, not the deskewed ones (backend_node.py:1872-1884): xyz_dev is what
+ * gcs_scan_inputs.xyz_dev holds.  xyz_format 0: float32 x, y, z at bytes 0, 4, 8 of a point_step-byte
+ * record (point_step >= 12, a multiple of 4); xyz_format 1: float64 at bytes 0, 8, 16 (point_step >= 24, a
+ * multiple of 8).  in->points_base and in->n_points are ignored.  Widening float32 is exact: the results
+ * are bit for bit those of gcs_camera_splats on the float64 array of the same values. */
+int gcs_camera_splats_scan(gcs_camsplat_ctx* ctx, const gcs_camsplat_inputs* in, const void* xyz_dev,
+                           int32_t point_step, int32_t xyz_format, int32_t n_points, gcs_camsplat_outputs* out);
 
 /* ---------------------------------------------------------------- primitive path: map rendering */
 /* The reference's output side (backend/rendering.py, common/bev_pushforward.py) on the GPU, reading
@@ -1074,7 +1082,8 @@ typedef struct {
   int32_t n_points;
   gcs_surfel_outputs* surfel_out;  /* device pointers: the batch's LiDAR slice + the extractor arrays */
   int32_t* lidar_sources_dev;      /* the batch's sources from the LiDAR slice start: 1 on valid rows */
-  gcs_assoc_meas meas;             /* the whole MeasurementBatch; n_valid is set from the surfel count */
+  gcs_assoc_meas meas;             /* the whole MeasurementBatch; n_valid is set by the call (the camera count;
+                                      the surfel count is added on the device) */
   const double* batch_colors;      /* n_total x 3 (step 12b) */
   const int32_t* batch_sources;    /* n_total (step 12b) */
   gcs_pmap_view* view;             /* n_stencil x m_tile_view rows */
@@ -1098,8 +1107,9 @@ typedef struct {
   double phase_us[12];  /* host clock since the call's entry: [0] begin returned, [1] surfels queued,
                            [3] recency / view / association / pose evidence queued, [4] the one wait for them
                            returned and their results collected, [5] finish returned, [6] step 12b queued;
-                           [7] gcs_live_collect's wait (set by gcs_live_collect); [2], [8]-[11] unused (the
-                           surfel count is read on the device) */
+                           [7] gcs_live_collect's wait (set by gcs_live_collect); [8] the camera slice queued
+                           (gcs_live_scan_camera: form A ahead of the begin, form B ahead of the surfels);
+                           [2], [9]-[11] unused (the surfel count is read on the device) */
   /* after gcs_live_collect */
   gcs_pmap_update_stats update;
   int32_t counts[GCS_LIVE_MAX_TILES];              /* valid counts of the active tiles */
@@ -1111,6 +1121,38 @@ typedef struct {
 int gcs_live_scan(gcs_ctx* ctx, const gcs_scan_inputs* in, gcs_scan_begin_outputs* begin, const gcs_live_args* a,
                   gcs_live_outputs* lo, gcs_scan_outputs* out);
 int gcs_live_collect(gcs_ctx* ctx, gcs_live_outputs* lo);
+
+/* The camera slice of the chain's batch (rows [0, n_feat) of a->meas's arrays), in one of two forms.
+ * Form A (ctx != NULL): the slice is built in the chain, as the node builds it ahead of its hypothesis
+ * loop (backend_node.py:1865-1925).  gcs_camera_splats_scan's kernels on the scan's records (xyz_dev /
+ * point_step / xyz_format / n_points; in->points_base and in->n_points are ignored) are the first work
+ * queued on the context's stream, ahead of gcs_scan_begin's host prologue -- they depend on nothing the
+ * begin produces and run under its host work -- so a->zero_dev is zeroed ahead of them.  out's batch
+ * pointers are row 0 of the batch's own arrays; its diagnostics may be NULL.
+ * Form B (ctx == NULL): a slice built earlier by gcs_camera_splats.  The n_feat rows of src's nine batch
+ * arrays are copied device to device into out's on the stream, after the zeroing; src->n_camera_valid is
+ * the camera count.
+ * Either way the association and the pose evidence see n_camera_valid + the surfel count rows; the
+ * certificates' sums follow the per-operator path (the surfel certificate's ESS is the LiDAR count).
+ * out->n_camera_valid is set when the call returns GCS_OK. */
+typedef struct {
+  gcs_camsplat_ctx* ctx;               /* form A; NULL: form B */
+  const gcs_camsplat_inputs* in;       /* form A */
+  const void* xyz_dev;                 /* form A: the scan's records (gcs_scan_inputs.xyz_dev) */
+  int32_t point_step, xyz_format, n_points;
+  const gcs_camsplat_outputs* src;     /* form B */
+  int32_t n_feat;                      /* form B: rows of the camera slice */
+  gcs_camsplat_outputs* out;           /* both: the batch's camera slice (and form A's diagnostics) */
+} gcs_live_camera;
+
+/* gcs_live_scan with a camera slice (cam == NULL: gcs_live_scan itself, bit for bit).  A feature over
+ * max_candidates (form A) is found at the chain's one wait, before gcs_scan_finish: the call returns
+ * GCS_ERR_STATE with gcs_camera_splats' message, the belief is not advanced and step 12b is not queued;
+ * the map is as after the recency inflation and lo's created tiles are to be adopted -- what any failure
+ * between the begin and the finish leaves (a failed launch or wait there returns at the same point). */
+int gcs_live_scan_camera(gcs_ctx* ctx, const gcs_scan_inputs* in, gcs_scan_begin_outputs* begin,
+                         const gcs_live_args* a, const gcs_live_camera* cam, gcs_live_outputs* lo,
+                         gcs_scan_outputs* out);
 /* the MA-hex tile ids of tiling.py:167-209 (ma_hex_stencil_tile_ids) around center; returns the count
  * (or GCS_ERR_ARG when it exceeds cap) */
 int gcs_ma_hex_stencil(const double* center3, double h_tile, int32_t radius_xy, int32_t radius_z, int64_t* out,
