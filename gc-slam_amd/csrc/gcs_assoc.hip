@@ -38,69 +38,14 @@ namespace gcs {
 namespace {
 
 constexpr int kAsThreads = 256;
-#ifndef GCS_POOL_THREADS
-#define GCS_POOL_THREADS 128
-#endif
-constexpr int kPoolThreads = GCS_POOL_THREADS;
-#ifndef GCS_POOL_FLAT
-#define GCS_POOL_FLAT 1  // 0: each trip's position loads wait on its flag loads (A/B)
-#endif
-#ifndef GCS_POOL_PB
-#define GCS_POOL_PB 8  // pool entries per thread and trip
-#endif
+constexpr int kPoolThreads = 128;
+constexpr int kPoolPB = 8;  // pool entries per thread and trip
 // the Sinkhorn workgroup: 8 waves, 4 rows per thread at K <= 8 (K_mat rows in registers).  1024
 // threads (4 waves per SIMD, 128 VGPRs: the rows spill) measured slower: 3.2 vs 3.0 us per iteration,
 // 0.480 vs 0.422 ms per call (profiles/r03/assoc/)
-#ifndef GCS_SH_THREADS
-#define GCS_SH_THREADS 512
-#endif
-constexpr int kShThreads = GCS_SH_THREADS;
-#ifndef GCS_SH_ONEBAR
-// 1: v in every wave, one barrier per iteration -- no faster while v took a pow (profiles/r04/sh1/),
-// 0.150 -> 0.144 ms per call with the Newton root (profiles/r05/assoc/); 0: v by wave 0 + a second barrier
-#define GCS_SH_ONEBAR 1
-#endif
-#ifndef GCS_SH_LOGB
-#define GCS_SH_LOGB 1  // 0: v = pow(b / K^T u, vb) with the quotient in every iteration (A/B)
-#endif
-#ifndef GCS_SH_TAB
-#define GCS_SH_TAB 1  // 0: the loop's log / exp are log_fast / exp_fast (fdlibm forms with a divide; A/B)
-#endif
-#ifndef GCS_SH_ILV
-#define GCS_SH_ILV 1  // 0: each row's u under its own branches (the chains one after another; A/B)
-#endif
-#ifndef GCS_SH_SPLIT
-#define GCS_SH_SPLIT 1  // 0: log_tab / exp_tab called whole per row (their table reads not hoisted; A/B)
-#endif
-#ifndef GCS_SH_ZSKIP
-#define GCS_SH_ZSKIP 1  // 0: zero-marginal rows take the fallback branch (A/B)
-#endif
-#ifndef GCS_SH_LOGA
-#define GCS_SH_LOGA 1  // 0: u = pow(a / Kv, ua) with the quotient in every iteration (A/B)
-#endif
-#ifndef GCS_SH_DPP
-#define GCS_SH_DPP 1  // 0: the Sinkhorn's reduce-scatter through ds_bpermute xor shuffles (A/B)
-#endif
-#ifndef GCS_SH_ROOT
-#define GCS_SH_ROOT 1  // 0: no Newton root for exponents 1 / n (the log / exp tables every iteration; A/B)
-#endif
+constexpr int kShThreads = 512;
 constexpr int kShCR = 16 * 1024 / kShThreads;  // Sinkhorn row capacity: N <= kShCR * kShThreads / KM
 constexpr int kMaxStencil = 64;
-// GCS_SH_PROBE (timing probe builds only): wall-clock stamps of the Sinkhorn's phases, printed by the
-// host call (stderr) -- workgroup 0: start, marginal, K_mat, loop end, end; workgroup 1: end
-#ifndef GCS_SH_PROBE
-#define GCS_SH_PROBE 0
-#endif
-#if GCS_SH_PROBE
-__device__ unsigned long long g_sh_stamp[16];
-#define SH_STAMP(k) do { if (threadIdx.x == 0) g_sh_stamp[k] = wall_clock64(); } while (0)
-// the iteration's parts, summed over the iterations by thread 0 (u, K^T u + reduce-scatter, first
-// barrier, v, second barrier + v read)
-#define SH_ACC(k) do { const unsigned long long tn_ = wall_clock64(); sh_pa[k] += tn_ - sh_tp; sh_tp = tn_; } while (0)
-#else
-#define SH_STAMP(k) do { } while (0)
-#define SH_ACC(k) do { } while (0)
-#endif
 constexpr double kLog4Pi = 2.5310242469692907;     // np.log(4.0 * np.pi)
 constexpr double kLog2 = 0.6931471805599453;       // np.log(2.0)
 constexpr double kSqrt3Half = 0.8660254037844386;  // jnp.sqrt(3.0) * 0.5 (:319)
@@ -114,7 +59,7 @@ struct AsParams {
   int n, m_view, m_shift, n_tiles, n_stencil, k, iters, m_pool;
   int s_center;  // the stencil entry (0, 0, 0): the row's own tile
   int a_policy, row_min, med;
-  int fin_split;  // the finish (pi, responsibilities, certificate sums): GCS_SH_FINSPLIT's modes
+  int fin_split;  // the finish (pi, responsibilities, certificate sums): GCSLAM_SH_FINSPLIT's modes
   unsigned epoch; // this launch's hand-off value of the Sinkhorn's flag (never 0)
   double beta, eps, tau_a, tau_b, eps_mass, eps_lift, eps_dir, h, lam, eps_lam;
   long long scan_seq;
@@ -352,8 +297,7 @@ __device__ __forceinline__ bool kless(unsigned long long ka, int pa, unsigned lo
 
 // one workgroup per measurement row: kPoolThreads = 128 (two waves) puts all 1,536 rows of the reference
 // sizes in flight at once (eight workgroups per CU by registers and LDS); 256 threads took two rounds
-// of workgroups (GCS_POOL_THREADS=256 for A/B; any split of the pool over the lanes gives the same
-// candidates, see the merge below)
+// of workgroups (any split of the pool over the lanes gives the same candidates, see the merge below)
 template <int KM>
 __global__ __launch_bounds__(kPoolThreads) void k_as_pool(AsIn in, AsParams p, AsWork w, AsOut o) {
 #pragma clang fp contract(off)
@@ -384,7 +328,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_as_pool(AsIn in, AsParams p, A
     const bool prune = p.beta >= 0.0;
     // PB pool entries per trip, in increasing pool position: their flag and position loads issue
     // together, none behind another's result (the pass is bound by L2 round trips, not VALU)
-    constexpr int PB = GCS_POOL_PB;
+    constexpr int PB = kPoolPB;
     // Block threshold (beta >= 0): cost = d_pos + beta d_dir lies in [d_pos, d_pos + beta] (d_dir in
     // [0, 1], rounding monotone), so with D an upper bound of the row's K-th smallest valid d_pos at
     // least K entries cost <= D + beta: an entry with d_pos > D + beta cannot be selected and needs no
@@ -404,7 +348,6 @@ __global__ __launch_bounds__(kPoolThreads) void k_as_pool(AsIn in, AsParams p, A
           if (ti < 0) continue;
           const size_t base = (size_t)ti * MV;
           for (int o = t; o < MV; o += PB * kPoolThreads) {
-#if GCS_POOL_FLAT
             uint8_t vv[PB];
             double px[PB], py[PB], pz[PB];
 #pragma unroll
@@ -422,18 +365,6 @@ __global__ __launch_bounds__(kPoolThreads) void k_as_pool(AsIn in, AsParams p, A
               const double dx = mp[0] - px[u], dy = mp[1] - py[u], dz = mp[2] - pz[u];
               dmin = fmin(dmin, (dx * dx + dy * dy) + dz * dz);
             }
-#else
-#pragma unroll
-            for (int u = 0; u < PB; ++u) {
-              const int oo = o + u * kPoolThreads;
-              if (oo >= MV) break;
-              const size_t e = base + oo;
-              if (!in.vvalid[e]) continue;
-              const double dx = mp[0] - in.vpos[3 * e], dy = mp[1] - in.vpos[3 * e + 1],
-                           dz = mp[2] - in.vpos[3 * e + 2];
-              dmin = fmin(dmin, (dx * dx + dy * dy) + dz * dz);
-            }
-#endif
           }
         }
         double kth = INFINITY, cur = dmin;
@@ -482,7 +413,6 @@ __global__ __launch_bounds__(kPoolThreads) void k_as_pool(AsIn in, AsParams p, A
       const int ti = s_tix[sq];
       const size_t base = (size_t)(ti < 0 ? 0 : ti) * MV;
       for (int ow = t & ~63; ow < MV; ow += PB * kPoolThreads) {  // wave-uniform trips (ballots inside)
-#if GCS_POOL_FLAT
         uint8_t vv[PB];
         double px[PB], py[PB], pz[PB];
 #pragma unroll
@@ -494,7 +424,6 @@ __global__ __launch_bounds__(kPoolThreads) void k_as_pool(AsIn in, AsParams p, A
           py[u] = in.vpos[3 * e + 1];
           pz[u] = in.vpos[3 * e + 2];
         }
-#endif
 #pragma unroll
         for (int u = 0; u < PB; ++u) {
           const int oo = ow + lane + u * kPoolThreads;
@@ -502,14 +431,8 @@ __global__ __launch_bounds__(kPoolThreads) void k_as_pool(AsIn in, AsParams p, A
           const int q = sq * MV + oo;
           bool valid = false;
           double d_pos = 0.0;
-#if GCS_POOL_FLAT
           if (in_tile && vv[u]) {
             const double dx = mp[0] - px[u], dy = mp[1] - py[u], dz = mp[2] - pz[u];
-#else
-          if (in_tile && ti >= 0 && in.vvalid[base + oo]) {
-            const size_t e = base + oo;
-            const double dx = mp[0] - in.vpos[3 * e], dy = mp[1] - in.vpos[3 * e + 1], dz = mp[2] - in.vpos[3 * e + 2];
-#endif
             d_pos = (dx * dx + dy * dy) + dz * dz;
             valid = true;
           } else if (in_tile) {
@@ -615,7 +538,8 @@ __global__ __launch_bounds__(kPoolThreads) void k_as_pool(AsIn in, AsParams p, A
   }
 }
 
-// The pool by center-tile bucket (GCS_POOL_LDS).  Rows whose own tile is view tile c share their
+// The pool by center-tile bucket (the default; GCSLAM_POOL_LDS=0 turns it off).  Rows whose own tile
+// is view tile c share their
 // stencil's view tiles (the stencil is a fixed offset set around the row's cell), so the rows are
 // grouped by c (k_as_stage lays them out, each bucket padded to a chunk of kPoolLdsWaves rows) and a
 // workgroup of kPoolLdsWaves waves stages its chunk's stencil tiles in LDS once and each wave selects
@@ -637,27 +561,12 @@ __global__ __launch_bounds__(kPoolThreads) void k_as_pool(AsIn in, AsParams p, A
 // table distances (an order statistic of entrywise upper bounds bounds the exact one); an entry is
 // pruned only when its lower bound exceeds D + beta (threshold rounded up into f32); the list-max skip
 // uses the exact d_pos.  One wave per row: the lists' merge needs no block barrier.
-#ifndef GCS_POOL_LDS
-#define GCS_POOL_LDS 1
-#endif
 constexpr int kPoolLdsWaves = 8;
 constexpr int kLRing = 256;  // per wave: >= 63 pending + kLdsPB x 64 appended per trip
 constexpr int kLdsPB = 2;
 constexpr int kPoolLdsMaxView = (160 * 1024 - kPoolLdsWaves * kLRing * 8) / 16;  // 9,216 stencil slots
 constexpr int kMaxBuckets = 4096;
-constexpr int kBucketRows = 4;
-// GCS_POOL_PROBE (timing probe builds only): per row, wall-clock stamps of k_as_pool_lds's phases
-// (block start, staged, pass 1, ring + costing, merge, slow path, end) and the ring count, printed by
-// the host collect (stderr)
-#ifndef GCS_POOL_PROBE
-#define GCS_POOL_PROBE 0
-#endif
-#if GCS_POOL_PROBE
-__device__ unsigned long long g_pool_probe[4096 * 10];
-#define PP_STAMP(k) do { if (lane == 0) g_pool_probe[(size_t)i * 10 + (k)] = wall_clock64(); } while (0)
-#else
-#define PP_STAMP(k) do { } while (0)
-#endif  // rows per k_as_stage thread: <= 4,096 rows (the Sinkhorn caps them at 2,048)
+constexpr int kBucketRows = 4;  // rows per k_as_stage thread: <= 4,096 rows (the Sinkhorn caps them at 2,048)
 
 // workgroups 0..n_tiles-1: view tile b's valid entries in slot order (a block scan of wave ballots)
 // into vc[b MV ..] as (x, y, z, slot) in f32, their count in vcnt[b].  Workgroup n_tiles: each row's
@@ -776,7 +685,7 @@ __global__ __launch_bounds__(1024) void k_as_stage(AsIn in, AsParams p, AsWork w
   }
 }
 
-// GCS_PREP_FUSED: k_as_prep and k_as_stage as one launch for views of at most kFusedTiles tiles
+// The fused prep: k_as_prep and k_as_stage as one launch for views of at most kFusedTiles tiles
 // (1,024-thread blocks): the prep's row and view lanes, one block per view tile compacting it, and one
 // block that buckets the rows.  That block cannot read the row lanes' results (same launch), so it
 // recomputes what it needs from the inputs with the same device code: each row's mean position and
@@ -785,9 +694,6 @@ __global__ __launch_bounds__(1024) void k_as_stage(AsIn in, AsParams p, AsWork w
 // slower (profiles/r05/assoc/prepfused_*: the launch 29 us against 8.6 + 7.7 us for the two, the bucket
 // block's serial recomputation being the longest lane of it; C-ABI 0.156 vs 0.145 ms): off by default,
 // GCSLAM_PREP_FUSED=1 for A/B.
-#ifndef GCS_PREP_FUSED
-#define GCS_PREP_FUSED 0
-#endif
 constexpr int kFusedTiles = 256;
 constexpr int kFusedBuckets = kFusedTiles + 1;
 __global__ __launch_bounds__(1024) void k_as_prep_fused(AsIn in, AsParams p, AsWork w, const int8_t* __restrict__ st,
@@ -1072,7 +978,6 @@ __device__ __forceinline__ void pool_row(const AsIn& in, const AsParams& p, cons
       return (dx * dx + dy * dy) + dz * dz;
     };
     float thrA = INFINITY;  // prune an entry whose table distance^2 exceeds this
-    PP_STAMP(2);
     if (prune) {
       double thr = INFINITY;
       for (int round = 0; round < 2 && thr == INFINITY; ++round) {
@@ -1100,7 +1005,6 @@ __device__ __forceinline__ void pool_row(const AsIn& in, const AsParams& p, cons
         thrA = (float)(dl * dl * (1.0 + 0x1p-20));  // (rounded to f32: still above the f64 value)
       }
     }
-    PP_STAMP(3);
     unsigned head = 0, tail = 0;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     auto take = [&](int n) {  // lanes < n cost ring entry head + lane (exact f64)
@@ -1144,12 +1048,7 @@ __device__ __forceinline__ void pool_row(const AsIn& in, const AsParams& p, cons
       }
     }
     if (tail != head) take((int)(tail - head));
-    PP_STAMP(4);
-#if GCS_POOL_PROBE
-    if (lane == 0) g_pool_probe[(size_t)i * 10 + 8] = tail;
-#endif
     const unsigned long long kth_key = wave_merge<KM>(key, idx, p.k, lane, my_sel);
-    PP_STAMP(5);
     if (kth_key >= order_key(kCostInvalid)) {
       // Fewer than K valid entries cost less than the invalid cost.  No valid entry was pruned here
       // (a finite threshold has K valid entries at or below it, and a pruned one is above them all),
@@ -1198,12 +1097,8 @@ __device__ __forceinline__ void pool_row(const AsIn& in, const AsParams& p, cons
           cp = 0x7fffffff;
         }
       }
-#if GCS_POOL_PROBE
-      if (lane == 0) g_pool_probe[(size_t)i * 10 + 9] = 1;
-#endif
     }
   }
-  PP_STAMP(6);
   // per candidate (lane k < K): view index, unmasked cost + recency, row min (:377-403)
   const bool act = lane < p.k;
   const int sel_ti = __shfl(my_tix, row_valid && act ? my_sel / MV : 0, 64);
@@ -1240,7 +1135,6 @@ __device__ __forceinline__ void pool_row(const AsIn& in, const AsParams& p, cons
     const unsigned dist = (unsigned)__popcll(__ballot(cv && tile != -1 && !seen));
     if (lane == 0) w.cstat[i] = cnt | (dist << 16);
   }
-  PP_STAMP(7);
 }
 
 template <int KM>
@@ -1250,9 +1144,6 @@ __global__ __launch_bounds__(kPoolLdsWaves * 64) void k_as_pool_lds(AsIn in, AsP
   float4* s_vp = (float4*)smem;
   const int MV = p.m_view, S = p.n_stencil;
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-#if GCS_POOL_PROBE
-  const unsigned long long t_start = wall_clock64();
-#endif
   const int r0 = w.order[blockIdx.x * kPoolLdsWaves];
   const int i = w.order[blockIdx.x * kPoolLdsWaves + wid];
   const int my_st = lane < S ? w.ctile[(size_t)blockIdx.x * 64 + lane] : -1;  // (S <= 64: in every wave)
@@ -1295,13 +1186,6 @@ __global__ __launch_bounds__(kPoolLdsWaves * 64) void k_as_pool_lds(AsIn in, AsP
   }
   __syncthreads();
   if (i < 0) return;  // a bucket's padding (after the only block barrier)
-#if GCS_POOL_PROBE
-  if (lane == 0) {
-    g_pool_probe[(size_t)i * 10 + 0] = t_start;
-    g_pool_probe[(size_t)i * 10 + 1] = wall_clock64();
-    for (int q = 2; q < 10; ++q) g_pool_probe[(size_t)i * 10 + q] = 0;
-  }
-#endif
   int* rq = (int*)(smem + (size_t)lds_slots * 16) + wid * 2 * kLRing;
   int* re = rq + kLRing;
   if (lds) {  // the row's stencil tiles are the chunk's (lane s: tile, valid count)
@@ -1614,15 +1498,12 @@ __device__ __forceinline__ double pow_fast(double x, double y) {
   return exp_fast(a);
 }
 
-// GCS_SH_FINSPLIT: the Sinkhorn's finish over several workgroups, one row per thread -- pi = u K v, the
-// responsibilities and row masses, and the certificate sums (per workgroup in a fixed tree, then the
-// workgroups in index order by the last one to finish).  1 (default): extra workgroups of the Sinkhorn
-// launch, which load their rows' costs while workgroup 0 iterates and wait for its u / v hand-off
+// fin_split (GCSLAM_SH_FINSPLIT): the Sinkhorn's finish over several workgroups, one row per thread --
+// pi = u K v, the responsibilities and row masses, and the certificate sums (per workgroup in a fixed
+// tree, then the workgroups in index order by the last one to finish).  1 (default): extra workgroups
+// of the Sinkhorn launch, which load their rows' costs while workgroup 0 iterates and wait for its u / v hand-off
 // (sc1 stores + a flag); 2: a launch of its own after the Sinkhorn (k_as_finish); 0: workgroup 0
 // finishes alone (~13 us: three rows per thread, their loads and stores on one CU).
-#ifndef GCS_SH_FINSPLIT
-#define GCS_SH_FINSPLIT 1
-#endif
 template <int STEP>
 __device__ __forceinline__ double dsum_step(double x, int lane) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(x);
@@ -1772,16 +1653,10 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
                                                             const int32_t* n_valid_dev) {
 #pragma clang fp contract(off)
   __shared__ double s_red[16 * (KM + 8)];
-#if GCS_SH_ONEBAR
   __shared__ double s_colp2[2][(kShThreads / 64) * KM];  // alternate iterations (one barrier each)
-#else
-  __shared__ double s_colp[(kShThreads / 64) * KM];
-  __shared__ double s_v[KM];
-#endif
   __shared__ uint32_t s_hist[256], s_sel[4];
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int N = p.n, K = p.k;
-  if (blockIdx.x == 0) SH_STAMP(0);
   const bool empty = n_valid_host + (n_valid_dev ? *n_valid_dev : 0) == 0 || *w.mvalid == 0u;
   if (empty) {  // :272-287 -- zeros, exact cert (workgroup 0)
     if (blockIdx.x != 0) return;
@@ -1799,7 +1674,7 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
     cand_stats<kShThreads>(in, p, p.eps_mass, [](size_t) { return 0; }, o.cert);
     return;
   }
-  if (blockIdx.x >= 2) {  // a finish workgroup (GCS_SH_FINSPLIT 1): its rows' costs, then workgroup 0's u, v
+  if (blockIdx.x >= 2) {  // a finish workgroup (fin_split 1): its rows' costs, then workgroup 0's u, v
     __shared__ double s_fin[(kShThreads / 64) * (7 + KM)];
     __shared__ int s_ok;
     auto wait = [&]() -> bool {
@@ -1847,7 +1722,6 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
     const double p95_a = radix_select<RPT>(va1, oka1, std::min((int)(0.95 * (double)N), N - 1), s_hist, s_sel);
     const int nbt = N * K;
     const double p95_b_row = radix_select<RPT * KM>(brow1, okb1, std::min((int)(0.95 * (double)nbt), nbt - 1), s_hist, s_sel);
-    SH_STAMP(5);
     if (t == 0) {
       o.cert[CE_P95_A] = p95_a;
       o.cert[CE_B_P95] = p95_b_row;
@@ -1858,17 +1732,10 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
     cand_stats<kShThreads>(in, p, p.eps_mass, [cand](size_t q) { return (int)cand[q]; }, o.cert, w.cstat);
     return;
   }
-#if GCS_SH_TAB
   // the loop's log / exp tables (gcs_sh_tables.h) in LDS: per-lane indexed reads at LDS latency
   __shared__ double s_lt[kShLogTabLen], s_et[kShExpTabLen];
   for (int q = t; q < kShLogTabLen; q += kShThreads) s_lt[q] = kShLogTab[q];
   for (int q = t; q < kShExpTabLen; q += kShThreads) s_et[q] = kShExpTab[q];  // (bsum's barriers publish them)
-#define SH_LOG(x) log_tab((x), s_lt)
-#define SH_EXP(x) exp_tab((x), s_et)
-#else
-#define SH_LOG(x) log_fast(x)
-#define SH_EXP(x) exp_fast(x)
-#endif
   // marginal a (:412-424)
   double va[RPT], X[RPT * KM];  // X: the cost rows, then K_mat = exp(-C / eps) in place
   double part[1] = {0.0};
@@ -1884,17 +1751,14 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
   }
   bsum<1>(part, s_red);
   const double sum_a = fmax(part[0], p.eps_mass);
-  SH_STAMP(1);
 #pragma unroll
   for (int j = 0; j < RPT; ++j) va[j] = va[j] / sum_a;
-#if GCS_SH_LOGA
   // log a once: each iteration's u = (a / Kv)^ua is exp(ua (log a - log Kv)) -- the quotient (and its
   // rcp / Newton / residual steps) leaves the loop (rounding-level change; the tests' 1e-9 bars)
   double lva[RPT];
 #pragma unroll
   for (int j = 0; j < RPT; ++j)
     lva[j] = va[j] >= 2.2250738585072014e-308 && va[j] <= 1.7976931348623157e308 ? log_fast(va[j]) : NAN;
-#endif
   uint32_t okm = 0;
 #pragma unroll
   for (int j = 0; j < RPT; ++j)
@@ -1932,14 +1796,13 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
     const int n = r >= 1.0 && r <= 64.0 ? (int)rint(r) : 0;
     return n >= 1 && 1.0 / (double)n == e ? n : 0;
   };
-  const int na = GCS_SH_ROOT ? root_n(ua) : 0, nb = GCS_SH_ROOT ? root_n(vb) : 0;
+  const int na = root_n(ua), nb = root_n(vb);
   const double ina = na ? 1.0 / (double)na : 0.0, inb = nb ? 1.0 / (double)nb : 0.0;
   const float ina_f = (float)ina, inb_f = (float)inb;
   double apow[RPT];  // a^ua (the row's factor of u on the root path)
 #pragma unroll
   for (int j = 0; j < RPT; ++j) apow[j] = na ? pow_fast(va[j], ua) : 0.0;
   const double bpow = nb ? pow_fast(bk, vb) : 0.0;
-#if GCS_SH_LOGB
   // v = (b / (K^T u + 1e-12))^vb as exp(vb (log b - log K^T u)): log b once per call, no quotient in
   // the loop (as u; the short log / exp outside their ranges fall back to the quotient form)
   const double lbk = log(bk);
@@ -1951,18 +1814,14 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
       y = nb == 6 ? root_step_c<6>(y, ss, inb) : root_step(y, ss, nb, inb);
       return bpow * y;
     }
-    const double b_ = vb * (lbk - SH_LOG(ss));
+    const double b_ = vb * (lbk - log_tab(ss, s_lt));
     return ss >= 2.2250738585072014e-308 && ss <= 1.7976931348623157e308 && fabs(b_) < 700.0
-               ? SH_EXP(b_)
+               ? exp_tab(b_, s_et)
                : pow_fast(div_fast(bk, ss), vb);
   };
-#else
-  auto v_scale = [&](double sum) { return pow_fast(div_fast(bk, sum + 1e-12), vb); };
-#endif
   if (p.med)  // (else the pool kernel wrote K_mat)
 #pragma unroll
     for (int q = 0; q < RPT * KM; ++q) X[q] = ((okm >> q) & 1u) ? exp(-X[q] / eps) : 0.0;
-  SH_STAMP(2);
   double u[RPT], v[KM];
 #pragma unroll
   for (int j = 0; j < RPT; ++j) u[j] = 1.0;
@@ -1977,9 +1836,6 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
   int col = 0;  // the column this lane ends up holding
 #pragma unroll
   for (int s = 0; s < LG; ++s) col |= ((lane >> (5 - s)) & 1) << (LG - 1 - s);
-#if GCS_SH_PROBE
-  unsigned long long sh_pa[5] = {0, 0, 0, 0, 0}, sh_tp = wall_clock64();
-#endif
   for (int it = 0; it < p.iters; ++it) {
     // u = (a / (K v + 1e-12))^ua, one lane per row (K v in column order)
     // ua = fl(1 / na): u = a^ua (K v + 1e-12)^(-1/na), the rows side by side (na = 6, the reference
@@ -2017,11 +1873,9 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
     } else if (na) {
       root_rows(std::integral_constant<int, 0>{});
     } else {
-#if GCS_SH_LOGA && GCS_SH_ILV
-    // the rows' chains side by side, branch-free (log and exp of an in-range stand-in where the row's
-    // arguments are out of range), the rare fallback rows after them: the per-row branches serialised
-    // the RPT chains (K v -> log -> exp), which is the loop's critical path
-    {
+      // the rows' chains side by side, branch-free (log and exp of an in-range stand-in where the row's
+      // arguments are out of range), the rare fallback rows after them: the per-row branches serialised
+      // the RPT chains (K v -> log -> exp), which is the loop's critical path
       double kvv[RPT], a_[RPT], ue[RPT];
       bool ok[RPT];
 #pragma unroll
@@ -2032,7 +1886,6 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
         kvv[j] = kv + 1e-12;
         ok[j] = kvv[j] >= 2.2250738585072014e-308 && kvv[j] <= 1.7976931348623157e308;
       }
-#if GCS_SH_TAB && GCS_SH_SPLIT
       // every row's table reads first, then the polynomials
       double lm[RPT], li[RPT], lh[RPT], ll[RPT];
       int le[RPT], lj[RPT];
@@ -2059,56 +1912,16 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
       }
 #pragma unroll
       for (int j = 0; j < RPT; ++j) ue[j] = exp_tab_poly(er[j], em[j], eh[j], el[j]);
-#else
-#pragma unroll
-      for (int j = 0; j < RPT; ++j) {
-        a_[j] = ua * (lva[j] - SH_LOG(ok[j] ? kvv[j] : 1.0));
-        // (NaN lva: a zero or denormal marginal; |a_| >= 700; NaN a_ fails the compare)
-        ok[j] = ok[j] && fabs(a_[j]) < 700.0;
-      }
-#pragma unroll
-      for (int j = 0; j < RPT; ++j) ue[j] = SH_EXP(ok[j] ? a_[j] : 0.0);
-#endif
 #pragma unroll
       for (int j = 0; j < RPT; ++j) {
         const int r = t + j * kShThreads;
         double uj = ue[j];
         // a zero marginal (an invalid row) gives u = 0 exactly (pow_sinkhorn(0, ua)) without the
         // fallback branch, so waves holding invalid rows do not diverge into it every iteration
-#if GCS_SH_ZSKIP
         if (!ok[j] && va[j] != 0.0) uj = pow_fast(div_fast(va[j], kvv[j]), ua);
         u[j] = r < N && va[j] != 0.0 ? uj : 0.0;
-#else
-        if (!ok[j]) uj = pow_fast(div_fast(va[j], kvv[j]), ua);
-        u[j] = r < N ? uj : 0.0;
-#endif
       }
     }
-#else
-#pragma unroll
-    for (int j = 0; j < RPT; ++j) {
-      const int r = t + j * kShThreads;
-      double kv = 0.0;
-#pragma unroll
-      for (int k = 0; k < KM; ++k) kv = fma(X[j * KM + k], v[k], kv);
-#if GCS_SH_LOGA
-      const double kvv = kv + 1e-12;
-      double uj = 0.0;
-      if (r < N) {
-        const double a_ = ua * (lva[j] - SH_LOG(kvv));
-        // (NaN lva: a zero or denormal marginal; a Kv outside the short log's range; |a_| >= 700)
-        uj = kvv >= 2.2250738585072014e-308 && kvv <= 1.7976931348623157e308 && fabs(a_) < 700.0
-                 ? SH_EXP(a_)
-                 : pow_fast(div_fast(va[j], kvv), ua);
-      }
-      u[j] = uj;
-#else
-      u[j] = r < N ? pow_fast(div_fast(va[j], kv + 1e-12), ua) : 0.0;
-#endif
-    }
-#endif
-    }
-    SH_ACC(0);
     double c[KM];
 #pragma unroll
     for (int k = 0; k < KM; ++k) {
@@ -2118,8 +1931,8 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
       c[k] = sacc;
     }
     // reduce-scatter: step s exchanges half of the live values with a lane of the other half of its
-    // 64 >> s group (GCS_SH_DPP: xlane's DPP / permlane pairings -- xor 32, 16, then the mirrors -- in
-    // place of the ds_bpermute xor shuffles: each lane still ends with its column summed over all 64)
+    // 64 >> s group (xlane's DPP / permlane pairings -- xor 32, 16, then the mirrors -- in
+    // place of ds_bpermute xor shuffles: each lane still ends with its column summed over all 64)
 #pragma unroll
     for (int s = 0, n = KM; s < LG; ++s, n >>= 1) {
       const int h = n >> 1;
@@ -2129,23 +1942,13 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
         if (i < h) {
           const double send = up ? c[i] : c[i + h];
           const double keep = up ? c[i + h] : c[i];
-#if GCS_SH_DPP
           c[i] = keep + xlane_d(send, 5 - s, lane);
-#else
-          c[i] = keep + __shfl_xor(send, 32 >> s, 64);
-#endif
         }
       }
     }
     double cs = c[0];
-#if GCS_SH_DPP
 #pragma unroll
     for (int st = 5 - LG; st >= 0; --st) cs += xlane_d(cs, st, lane);
-#else
-#pragma unroll
-    for (int sh = (64 >> LG) / 2; sh >= 1; sh >>= 1) cs += __shfl_xor(cs, sh, 64);
-#endif
-#if GCS_SH_ONEBAR
     // every wave finishes v itself: lane k (< KM) sums column k over the waves in order and takes its
     // power, then v[k] comes from lane k.  The partials alternate between two buffers, so one barrier
     // per iteration separates a buffer's writes from its reads and from its next writes (a wave
@@ -2169,31 +1972,7 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
       const unsigned hi = __builtin_amdgcn_readlane((unsigned)(vbits >> 32), k);
       v[k] = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
     }
-#else
-    if ((lane & ((64 >> LG) - 1)) == 0) s_colp[wid * KM + col] = cs;
-    SH_ACC(1);
-    __syncthreads();
-    SH_ACC(2);
-    if (t < K) {  // v = (b / (K^T u + 1e-12))^vb: column t over the waves in order
-      double sum = s_colp[t];
-#pragma unroll
-      for (int g = 1; g < kShThreads / 64; ++g) sum += s_colp[g * KM + t];
-      s_v[t] = v_scale(sum);
-    }
-    SH_ACC(3);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < KM; ++k) v[k] = k < K ? s_v[k] : 0.0;
-    SH_ACC(4);
-#endif
   }
-  SH_STAMP(3);
-#if GCS_SH_PROBE
-  if (t == 0)
-    for (int k = 0; k < 5; ++k) g_sh_stamp[8 + k] = sh_pa[k];
-#endif
-#undef SH_LOG
-#undef SH_EXP
   if (p.fin_split) {  // the finish runs in other workgroups: hand them u, v and sum a
     // (sc1 stores drained by every storing wave, then one flag store: the guide's R1 publish)
 #pragma unroll
@@ -2258,9 +2037,7 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
     acc[3] += (rm - va[j]) * (rm - va[j]);
     acc[5] += va[j] > p.eps_mass ? 1.0 : 0.0;
   }
-  SH_STAMP(6);
   bsum<7 + KM>(acc, s_red);
-  SH_STAMP(7);
   if (t == 0) {
     double db = 0.0;
     for (int k = 0; k < K; ++k) db += (acc[7 + k] - bk) * (acc[7 + k] - bk);
@@ -2276,9 +2053,6 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
     o.cert[CE_NONZERO_A] = acc[5];
     o.cert[CE_NONZERO_B] = bk > p.eps_mass ? (double)K : 0.0;
     o.cert[CE_ESS] = acc[0] * acc[0] / (acc[1] + p.eps_mass);
-#if GCS_SH_PROBE
-    g_sh_stamp[4] = wall_clock64();
-#endif
     o.cert[CE_MASS_EPS] = p.eps_mass / (tm + p.eps_mass);
     o.cert[CE_TOTAL_COST] = acc[4];
     o.cert[CE_SUPPORT] = acc[5] / (double)std::max(N, 1);
@@ -2296,10 +2070,7 @@ __global__ __launch_bounds__(kShThreads) void k_as_sinkhorn(AsIn in, AsParams p,
 //   L_t += (sum_j r) Lambda_reg; h_t += Lambda_reg sum_j r (m - R p); cost_t += r q^T Lambda_reg q,
 //   q = m - R p - t (:121-148);  w = r sqrt(k kv + 1e-12), S += w v u^T, cost_r += w (1 - (R u).v)
 //   (:209-222).  out: L_t 9, h_t 3, cost_t, S 9, cost_r, sum row masses, rows used, map valid count.
-#ifndef GCS_VPE_THREADS
-#define GCS_VPE_THREADS 512  // 1024 capped the kernel at 128 VGPRs (73 spilled); at 512 it takes 193, no spills
-#endif
-constexpr int kVpeThreads = GCS_VPE_THREADS;
+constexpr int kVpeThreads = 512;  // 1024 capped the kernel at 128 VGPRs (73 spilled); at 512 it takes 193, no spills
 constexpr int kVpeVals = 27;
 struct VpeIn {
   const double *Lambdas, *thetas, *etas;
@@ -2365,13 +2136,10 @@ __device__ __forceinline__ void vpe_row(const VpeIn& in, int i, double* o) {
   o[24] = 1.0;
 }
 
-// GCS_VPE_SPLIT (default): every valid row's sums computed by its own lane over the grid (k_as_vpe_rows,
+// vpe_split (default): every valid row's sums computed by its own lane over the grid (k_as_vpe_rows,
 // rows x 25 in rowv), then k_as_vpe adds them in its per-thread row order -- the same additions on the
 // same values as the one-workgroup form (whose threads each walked three rows' candidate loads in
 // series: 29 us at the reference sizes).
-#ifndef GCS_VPE_SPLIT
-#define GCS_VPE_SPLIT 1
-#endif
 __global__ __launch_bounds__(256) void k_as_vpe_rows(VpeIn in, double* __restrict__ rowv) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= in.n || !in.valid[i]) return;
@@ -2464,15 +2232,13 @@ struct gcs_assoc_ctx {
   uint32_t* d_tcnt = nullptr;    // k_as_prep's per-view-tile valid counts (kMaxBuckets; zero between calls)
   double *d_su = nullptr, *d_fpart = nullptr;  // k_as_finish: u, v, sum a; per-workgroup sums
   uint32_t* d_ticket = nullptr;
-  int fin_split = GCS_SH_FINSPLIT;  // GCSLAM_SH_FINSPLIT: 0 the Sinkhorn workgroup, 2 a launch of its own (A/B)
+  int fin_split = 1;  // GCSLAM_SH_FINSPLIT: 0 the Sinkhorn workgroup, 2 a launch of its own (A/B)
   uint32_t* d_flag = nullptr;        // the Sinkhorn's hand-off flag
   uint32_t* d_cstat = nullptr;       // the pools' per-row candidate statistics
   unsigned epoch = 0;
-  bool pool_lds = GCS_POOL_LDS != 0;  // GCSLAM_POOL_LDS=0: k_as_pool from L2 for every view (A/B)
-  bool prep_fused = GCS_PREP_FUSED != 0;  // GCSLAM_PREP_FUSED=1: k_as_prep and k_as_stage as one launch (A/B)
-  bool vpe_split = GCS_VPE_SPLIT != 0;  // GCSLAM_VPE_SPLIT=0: the one-workgroup form (A/B, bitwise test)
-  int probe_iters = 0;       // GCS_SH_PROBE builds: the last launch's Sinkhorn iterations
-  int probe_rows = 0;        // GCS_POOL_PROBE builds: the last launch's rows
+  bool pool_lds = true;  // GCSLAM_POOL_LDS=0: k_as_pool from L2 for every view (A/B)
+  bool prep_fused = false;  // GCSLAM_PREP_FUSED=1: k_as_prep and k_as_stage as one launch (A/B)
+  bool vpe_split = true;  // GCSLAM_VPE_SPLIT=0: the one-workgroup form (A/B, bitwise test)
 };
 
 namespace {
@@ -2758,7 +2524,7 @@ int assoc_launch(gcs_assoc_ctx* c, const gcs_assoc_config* cfg, const gcs_assoc_
     if (nvh != 0 && mvh != 0) return as_fail(c, GCS_ERR_ARG, bad_policy);  // rearm zeroes the next counter
     // empty: the Sinkhorn kernel's zero path writes the reference's empty result
   }
-  const int nfin = (p.n + kFinThreads - 1) / kFinThreads;  // (GCS_SH_FINSPLIT 2)
+  const int nfin = (p.n + kFinThreads - 1) / kFinThreads;  // (fin_split 2)
   const int gsh = 2 + (p.fin_split == 1 ? (p.n + kShThreads - 1) / kShThreads : 0);  // the Sinkhorn's grid
   if (bad_policy) {
     hipLaunchKernelGGL((k_as_sinkhorn<8, rpt_for(8)>), dim3(2), dim3(kShThreads), 0, s, in, p, w, out, 0, (const int32_t*)nullptr);
@@ -2785,8 +2551,6 @@ int assoc_launch(gcs_assoc_ctx* c, const gcs_assoc_config* cfg, const gcs_assoc_
   }
   ASCHK(c, hipGetLastError());
   rearm.armed = false;  // the Sinkhorn is queued: it zeroes mv_next
-  c->probe_iters = p.iters;
-  c->probe_rows = p.n;
   return GCS_OK;
 }
 
@@ -2799,50 +2563,6 @@ int assoc_bind_stream(gcs_assoc_ctx* c, void* s) {
 }
 
 void assoc_collect(gcs_assoc_ctx* c, gcs_assoc_outputs* o) {
-#if GCS_SH_PROBE
-  {
-    unsigned long long h[16];
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_sh_stamp), sizeof(h));
-    fprintf(stderr, "sh_probe us: marginal %.2f kmat %.2f loop %.2f finish %.2f (pi %.2f bsum %.2f cert %.2f) | wg1 %.2f\n",
-            (h[1] - h[0]) / 100.0, (h[2] - h[1]) / 100.0, (h[3] - h[2]) / 100.0, (h[4] - h[3]) / 100.0,
-            (h[6] - h[3]) / 100.0, (h[7] - h[6]) / 100.0, (h[4] - h[7]) / 100.0, (h[5] - h[0]) / 100.0);
-    const double it = c->probe_iters > 0 ? 100.0 * c->probe_iters : 1.0;  // per iteration, us
-    fprintf(stderr, "sh_probe per iteration us: u %.3f KTu+scatter %.3f barrier1 %.3f v %.3f barrier2+read %.3f\n",
-            h[8] / it, h[9] / it, h[10] / it, h[11] / it, h[12] / it);
-  }
-#endif
-#if GCS_POOL_PROBE
-  {
-    static unsigned long long h[4096 * 10];
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pool_probe), sizeof(h));
-    const int n = std::min(c->probe_rows, 4096);
-    double sum[8] = {0}, mx[8] = {0}, ring = 0, rmax = 0;
-    int slow = 0, cnt = 0;
-    unsigned long long t0 = ~0ull, t1 = 0;
-    for (int i = 0; i < n; ++i) {
-      const unsigned long long* r = h + (size_t)i * 10;
-      if (!r[0] || !r[7]) continue;  // invalid rows skip stamps 2..6
-      ++cnt;
-      t0 = std::min(t0, r[0]);
-      t1 = std::max(t1, r[7]);
-      for (int k = 1; k < 8; ++k) {
-        unsigned long long prev = r[k - 1];
-        for (int j = k - 1; j >= 0 && !prev; --j) prev = r[j];
-        const double d = r[k] ? (double)(r[k] - prev) / 100.0 : 0.0;
-        sum[k] += d;
-        mx[k] = std::max(mx[k], d);
-      }
-      ring += (double)r[8];
-      rmax = std::max(rmax, (double)r[8]);
-      slow += (int)r[9];
-    }
-    if (cnt)
-      fprintf(stderr, "pool_probe rows %d span %.2f us | mean/max us: stage %.2f/%.2f pro %.2f/%.2f pass1 %.2f/%.2f "
-              "ring %.2f/%.2f merge %.2f/%.2f slow %.2f/%.2f final %.2f/%.2f | ring %.1f/%.0f slow rows %d\n",
-              cnt, (t1 - t0) / 100.0, sum[1] / cnt, mx[1], sum[2] / cnt, mx[2], sum[3] / cnt, mx[3], sum[4] / cnt, mx[4],
-              sum[5] / cnt, mx[5], sum[6] / cnt, mx[6], sum[7] / cnt, mx[7], ring / cnt, rmax, slow);
-  }
-#endif
   for (int q = 0; q < GCS_ASSOC_CERT_LEN; ++q) o->cert[q] = c->h_cert[q];
   o->exact = c->h_cert[CE_EXACT] != 0.0;
   o->n_map_valid = (int32_t)c->h_cert[CE_MVALID];

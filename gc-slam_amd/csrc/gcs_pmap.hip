@@ -513,17 +513,14 @@ __global__ __launch_bounds__(NT) void k_pm_select_reg(const uint64_t* __restrict
 // sorted[t M + r] = t M + slot for r < k.  Merge: an element's rank in the merged run is its own
 // index plus the count of the other run's smaller entries (binary search in LDS).  Runs live in
 // run_key / run_slot at the first leaf of their node (k entries per leaf); the writer's stores are
-// released (agent-scope fence, barrier) before its ticket, the second arrival acquires before reading.
-// GCS_TOPK_SC1 (default): the write-through run hand-off of cdna_hip_programming.md Guideline 16.
+// complete before its ticket, the second arrival acquires before reading: the write-through run
+// hand-off of cdna_hip_programming.md Guideline 16.
 // Hardware assumption (gfx950, not promised by the HIP / HSA memory model): agent-scope relaxed atomic
 // stores of the run go to the shared L2 (sc1) and complete before the storing wave passes
 // s_waitcnt vmcnt(0), so a relaxed ticket add after the workgroup barrier orders them for the second
 // arrival, whose one agent-scope acquire drops its CU's stale lines before it reads the run.  Checked
 // under repetition by tests/test_gpu_primitive_map.py::test_topk_tree_handoff_stress (24 views of seven
-// dense 50,000-slot tiles against the oracle's stable top-k); GCS_TOPK_SC1=0 builds the acq_rel ticket.
-#ifndef GCS_TOPK_SC1
-#define GCS_TOPK_SC1 1
-#endif
+// dense 50,000-slot tiles against the oracle's stable top-k).
 constexpr int kTopEpt = 4;                  // slots per thread in a leaf
 constexpr int kTopChunk = kTopEpt * kPmRed;  // slots per leaf: 4,096 (13 leaves, 4 merge levels at 50,000)
 constexpr int kTopMaxLevels = 8;             // up to 128 leaves per tile (M <= 524,288)
@@ -658,10 +655,9 @@ __global__ __launch_bounds__(kPmRed) void k_pm_topk(const uint64_t* __restrict__
     // publish this run, then take the node's ticket
     const size_t mine = (size_t)(i << lv) * k;
     uint32_t* ticket = tk + lv * kTopNodes + (i >> 1);
-#if GCS_TOPK_SC1
     // The hand-off of cdna_hip_programming.md Guideline 16 (counter form): the run is stored
     // write-through (agent-scope relaxed atomic stores: sc1), every wave drains its stores before the
-    // barrier, ONE lane adds to the ticket relaxed -- no release fence, whose L2 write-back the
+    // barrier, ONE lane adds to the ticket relaxed -- no release fence, whose L2 write-back an
     // acq_rel ticket paid once per workgroup and level -- and the second arrival's lane takes ONE
     // agent-scope acquire (the CU's stale lines dropped) before the workgroup's plain loads.
     for (int r = tid; r < L; r += kPmRed) {
@@ -680,22 +676,6 @@ __global__ __launch_bounds__(kPmRed) void k_pm_topk(const uint64_t* __restrict__
       s_go = old;
     }
     __syncthreads();
-#else
-    for (int r = tid; r < L; r += kPmRed) {
-      rk[mine + r] = s_k[r];
-      rs[mine + r] = s_s[r];
-    }
-    // every wave's stores drained at the barrier, then ONE agent-scope release with the ticket (a
-    // fence per thread wrote the L2 back once per wave: 0.75 ms per call), and the second arrival's
-    // acquire on the same atomic before the workgroup reads the sibling's run
-    __syncthreads();
-    if (tid == 0) {
-      const uint32_t old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-      if (old != 0u) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed
-      s_go = old;
-    }
-    __syncthreads();
-#endif
     if (s_go == 0u) return;  // the sibling merges
     const int Ls = topk_len(M, k, lv, sib);
     const size_t other = (size_t)(sib << lv) * k;
@@ -1197,16 +1177,13 @@ __global__ __launch_bounds__(kPmThreads) void k_pm_fuse_keys_blocks(PmStore st, 
   vals[g] = (uint32_t)g;
 }
 
-// The fuse's (key, row) sort for up to kSsWideMax rows in two launches (GCS_FUSE_SMALLSORT; rocPRIM's
+// The fuse's (key, row) sort for up to kSsWideMax rows in two launches (GCSLAM_FUSE_SMALLSORT=0: rocPRIM's
 // radix sort took five launches at these sizes -- a block sort and four merge passes, ~33 us plus their
 // host dispatch).  Each pair is one u64 (key << 32 | row), so the pairs are distinct and their order is
 // the stable key order.  k_ss_block: 1,024-pair runs sorted in LDS (bitonic); k_ss_merge: every pair's
 // final position = its rank in its run + the pairs below it in every other run (a binary search of each
 // run, the runs staged in LDS sixteen at a time: one group up to kSsMax rows -- the reference's 1,536 x 8
 // fuse rows --, four groups up to kSsWideMax), then the scatter.
-#ifndef GCS_FUSE_SMALLSORT
-#define GCS_FUSE_SMALLSORT 1
-#endif
 constexpr int kSsRun = 1024;
 constexpr int kSsMax = 16 * kSsRun;  // 128 KB of runs in k_ss_merge's LDS: one group
 constexpr int kSsWideMax = 4 * kSsMax;  // 65,536 rows: four groups
@@ -1277,74 +1254,22 @@ __global__ __launch_bounds__(kSsRun) void k_ss_merge(const uint64_t* __restrict_
 
 // Long runs of one (tile, slot, block) key -- many measurements associated to the same primitive, as
 // in a sparse map -- were one lane's serial walk (the live path's map update spent 0.5 ms in it).  A run
-// longer than kFuseChunk (32) rows is cut into chunks: the run's first chunk ends at the first position
-// b with b % kFuseChunk == 0 and b - kFuseChunk at or after the run start, later chunks at every such
-// b; one lane per chunk sums its rows in row order into P (field-major, kFT fields) and its length
-// into Lc, and the group's lane adds the chunk sums in order.  Runs of at most kFuseChunk rows are
-// never cut: their sums are bitwise the per-row walk's.  (Deterministic either way.)
+// longer than kFuseChunk (32) rows is summed ahead of the apply step (k_pm_fuse_runs, below) into P
+// (field-major, kFT fields) with its length in Lc, both at the run's first position; the group's lane
+// in k_pm_fuse_apply_blocks adds that sum in place of the rows.  Runs of at most kFuseChunk rows are
+// never summed ahead: their sums are bitwise the per-row walk's.  (Deterministic either way.)
 constexpr int kFuseChunk = 32;
 constexpr int kFT = 28;  // L 9 | theta 3 | eta 9 | r w | r | camera w | lidar w | rgb accumulation 3
 __device__ __forceinline__ bool fuse_long_start(const uint32_t* keys, int n, int pos, uint32_t key) {
   if (pos == 0 || keys[pos - 1] != key) return pos + kFuseChunk < n && keys[pos + kFuseChunk] == key;
   return pos % kFuseChunk == 0 && pos >= kFuseChunk && keys[pos - kFuseChunk] == key;
 }
-__global__ __launch_bounds__(kPmThreads) void k_pm_fuse_chunks(PmRows r, const uint32_t* keys, const uint32_t* vals,
-                                                               double* P, int* Lc, uint32_t nokey) {
-#pragma clang fp contract(off)
-  const int pos = blockIdx.x * kPmThreads + threadIdx.x;
-  if (pos >= r.n) return;
-  const uint32_t key = keys[pos];
-  if (key == nokey || !fuse_long_start(keys, r.n, pos, key)) return;
-  constexpr int ne = 3 * kNL;
-  static_assert(9 + 3 + ne + 4 + 3 == kFT, "fuse chunk layout");
-  double dL[9], dth[3], de[ne], dw = 0.0, drs = 0.0, dcam = 0.0, dlid = 0.0, dacc[3] = {0.0, 0.0, 0.0};
-  for (int c = 0; c < 9; ++c) dL[c] = 0.0;
-  for (int c = 0; c < 3; ++c) dth[c] = 0.0;
-  for (int c = 0; c < ne; ++c) de[c] = 0.0;
-  // the chunk's end first (contiguous key reads), then the rows with a known trip count, so that
-  // several rows' loads are in flight at once (the sum itself stays in row order)
-  int end = pos + 1;
-  while (end < r.n && keys[end] == key && !(end % kFuseChunk == 0 && keys[end - kFuseChunk] == key)) ++end;
-#pragma unroll 2
-  for (int q = pos; q < end; ++q) {
-    const size_t row = vals[q];
-    const double rr = r.resp[row] * 1.0;
-    for (int c = 0; c < 9; ++c) dL[c] = dL[c] + rr * r.lam[9 * row + c];
-    for (int c = 0; c < 3; ++c) dth[c] = dth[c] + rr * r.th[3 * row + c];
-    for (int c = 0; c < ne; ++c) de[c] = de[c] + rr * r.eta[(size_t)ne * row + c];
-    const double rw = rr * r.w[row];
-    dw = dw + rw;
-    drs = drs + rr;
-    if (r.src) {
-      const int sv = r.src[row];
-      const double wc = rw * (sv == 0 ? 1.0 : 0.0);
-      dcam = dcam + wc;
-      dlid = dlid + rw * (sv == 1 ? 1.0 : 0.0);
-      if (r.col)
-        for (int c = 0; c < 3; ++c) dacc[c] = dacc[c] + clip01(r.col[3 * row + c]) * wc;
-    }
-  }
-  const size_t n = (size_t)r.n;
-  for (int c = 0; c < 9; ++c) P[c * n + pos] = dL[c];
-  for (int c = 0; c < 3; ++c) P[(9 + c) * n + pos] = dth[c];
-  for (int c = 0; c < ne; ++c) P[(12 + c) * n + pos] = de[c];
-  P[21 * n + pos] = dw;
-  P[22 * n + pos] = drs;
-  P[23 * n + pos] = dcam;
-  P[24 * n + pos] = dlid;
-  for (int c = 0; c < 3; ++c) P[(25 + c) * n + pos] = dacc[c];
-  Lc[pos] = end - pos;
-}
-
-// GCS_FUSE_RUNS (default): a long run is summed by one wave instead of chunk by chunk -- lane l takes
-// rows start + l, + 64, ... in order, the lanes meet in a fixed xor tree -- and stored as one chunk of
-// the run's length (k_pm_fuse_apply_blocks then adds one sum per long run).  The chunk walk was a
-// serial chain of dependent row loads per lane (up to 63 rows): 40-50 us per map update on scans
-// whose sparse map draws hundreds of associations to one primitive.  Deterministic either way; runs of
-// at most kFuseChunk rows are untouched (the per-row walk's sums).
-#ifndef GCS_FUSE_RUNS
-#define GCS_FUSE_RUNS 1
-#endif
+// A long run is summed by one wave -- lane l takes rows start + l, + 64, ... in order, the lanes meet
+// in a fixed xor tree -- and stored as one chunk of the run's length at the run's first position
+// (k_pm_fuse_apply_blocks then adds one sum per long run).  A walk chunk by chunk, one lane per 32-row
+// chunk, was a serial chain of dependent row loads per lane (up to 63 rows): 40-50 us per map update on
+// scans whose sparse map draws hundreds of associations to one primitive.  Deterministic; runs of at
+// most kFuseChunk rows are untouched (the per-row walk's sums).
 __global__ __launch_bounds__(kPmThreads) void k_pm_fuse_runs(PmRows r, const uint32_t* keys, const uint32_t* vals,
                                                              double* P, int* Lc, uint32_t nokey) {
 #pragma clang fp contract(off)
@@ -1424,7 +1349,7 @@ __global__ __launch_bounds__(kPmThreads) void k_pm_fuse_runs(PmRows r, const uin
 }
 
 // one lane per (tile, slot) group: for each block in order, d = the block's rows summed in row order
-// (a long run: its chunk sums in order, k_pm_fuse_chunks), then slot += d -- the reference's
+// (a long run: the sum k_pm_fuse_runs stored at its first position), then slot += d -- the reference's
 // block-by-block fuse calls (pipeline.py:1272-1327)
 __global__ __launch_bounds__(kPmThreads) void k_pm_fuse_apply_blocks(PmStore st, const int32_t* tiles, PmRows r,
                                                                      const uint32_t* keys, const uint32_t* vals,
@@ -2109,7 +2034,7 @@ struct gcs_pmap {
   void* ftemp = nullptr;
   size_t ftemp_bytes = 0;
   int frows = 0;
-  double* fterm = nullptr;  // step 12b: chunk sums of long fuse runs (k_pm_fuse_chunks), grown
+  double* fterm = nullptr;  // step 12b: the sums of long fuse runs (k_pm_fuse_runs, field-major), grown
   int* flen = nullptr;
   size_t fterm_n = 0;
   uint32_t* mark = nullptr;  // fuse: slots seen (n_fused)
@@ -2687,7 +2612,7 @@ int fuse_blocks(gcs_pmap* p, int32_t n, const gcs_pmap_rows* rows, int nb, int r
                      (const int32_t*)p->d_tiles, timestamp, r, n, p->M, nb, rpb, p->fk, p->fv, p->bmark, d_err, nokey);
   static const bool small_sort = [] {
     const char* e = getenv("GCSLAM_FUSE_SMALLSORT");
-    return GCS_FUSE_SMALLSORT && !(e && e[0] == '0');
+    return !(e && e[0] == '0');
   }();
   if (small_sort && R <= kSsWideMax && p->ftemp_bytes >= (size_t)((R + kSsRun - 1) / kSsRun) * kSsRun * 8) {
     const int nrun = (R + kSsRun - 1) / kSsRun;
@@ -2708,12 +2633,8 @@ int fuse_blocks(gcs_pmap* p, int32_t n, const gcs_pmap_rows* rows, int nb, int r
     PMCHK(p, hipMalloc(&p->fterm, p->fterm_n * sizeof(double)));
     PMCHK(p, hipMalloc(&p->flen, (p->fterm_n / kFT) * sizeof(int)));
   }
-  if (GCS_FUSE_RUNS)
-    hipLaunchKernelGGL(k_pm_fuse_runs, dim3(rb), dim3(kPmThreads), 0, p->stream, r, (const uint32_t*)p->fk_s,
-                       (const uint32_t*)p->fv_s, p->fterm, p->flen, nokey);
-  else
-    hipLaunchKernelGGL(k_pm_fuse_chunks, dim3(rb), dim3(kPmThreads), 0, p->stream, r, (const uint32_t*)p->fk_s,
-                       (const uint32_t*)p->fv_s, p->fterm, p->flen, nokey);
+  hipLaunchKernelGGL(k_pm_fuse_runs, dim3(rb), dim3(kPmThreads), 0, p->stream, r, (const uint32_t*)p->fk_s,
+                     (const uint32_t*)p->fv_s, p->fterm, p->flen, nokey);
   hipLaunchKernelGGL(k_pm_fuse_apply_blocks, dim3(rb), dim3(kPmThreads), 0, p->stream, p->st, (const int32_t*)p->d_tiles,
                      r, (const uint32_t*)p->fk_s, (const uint32_t*)p->fv_s, nb, (long long)scan_seq,
                      (const double*)p->fterm, (const int*)p->flen, nokey);

@@ -277,13 +277,13 @@ def association_cert(o, config: AssociationConfig, N: int, chart_id: str = CHART
 _associators = {}
 
 
-ASSOC_ROW_SLOTS = 16384  # kShCR * kShThreads (gcs_assoc.hip:87): the Sinkhorn workgroup's K_mat registers
-ASSOC_MAX_K = 32         # gcs_assoc_ctx_create's max_k bound (gcs_assoc.hip:2560)
+ASSOC_ROW_SLOTS = 16384  # kShCR * kShThreads (gcs_assoc.hip:47): the Sinkhorn workgroup's K_mat registers
+ASSOC_MAX_K = 32         # gcs_assoc_ctx_create's max_k bound (gcs_assoc.hip:2326)
 
 
 def assoc_row_capacity(k: int) -> int:
     """Rows one call may hold at k_assoc = k: ASSOC_ROW_SLOTS // KM with the kernels' template width
-    KM = 8, 16, 32 for k <= 8, <= 16, <= 32 (max_rows_for, gcs_assoc.hip:2491): 2,048, 1,024, 512."""
+    KM = 8, 16, 32 for k <= 8, <= 16, <= 32 (max_rows_for, gcs_assoc.hip:2257): 2,048, 1,024, 512."""
     k = int(k)
     if k < 1 or k > ASSOC_MAX_K:
         raise ValueError(f"k_assoc = {k} outside [1, {ASSOC_MAX_K}]")

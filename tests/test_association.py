@@ -108,7 +108,7 @@ def test_assoc_ctx_argument_checks(lib):
 
 
 def _ctx_create_accepts(max_meas, max_pool, max_k):
-    """gcs_assoc_ctx_create's argument check (gcs_assoc.hip:2560) with max_rows_for (:2491) and
+    """gcs_assoc_ctx_create's argument check (gcs_assoc.hip:2326) with max_rows_for (:2257) and
     kShCR * kShThreads = 16 * 1024 (:87) restated."""
     max_rows = 16 * 1024 // (8 if max_k <= 8 else (16 if max_k <= 16 else 32))
     return not (max_meas < 1 or max_pool < 1 or max_k < 1 or max_k > 32 or max_meas > max_rows)

@@ -1,4 +1,4 @@
-"""OT association on the GPU at every shape-dependent path of assoc_launch (gcs_assoc.hip:2620-2790):
+"""OT association on the GPU at every shape-dependent path of assoc_launch (gcs_assoc.hip:2386-2555):
 the three template widths KM = 8, 16, 32 with k_assoc below and at the width, the row counts where the
 Sinkhorn's rows-per-thread form changes and where the row capacity is met, view strides that are no
 power of two, views past the prep's LDS tile table and past the bucket table, a stencil too large for
@@ -28,11 +28,11 @@ from test_gpu_association import _batch, _check, _run_both, _view
 pytestmark = pytest.mark.gpu
 
 # the library's constants the cases' guards depend on
-ROW_SLOTS = 16 * 1024        # kShCR * kShThreads, gcs_assoc.hip:87 (row capacity ROW_SLOTS // KM, :2491)
-SH_THREADS_X3 = 3 * 512      # k_as_sinkhorn<8, 3> serves n <= 3 * kShThreads, gcs_assoc.hip:57, :2768
-POOL_LDS_MAX_VIEW = 9216     # kPoolLdsMaxView, gcs_assoc.hip:646: lds_slots = 0 past it (:2743)
-LDS_TILES = 256              # kLdsTiles, gcs_assoc.hip:319 (k_as_prep's tile table) = kFusedTiles, :791
-MAX_BUCKETS = 4096           # kMaxBuckets, gcs_assoc.hip:647: n_tiles + 1 > 4096 leaves the bucketed pool (:2696)
+ROW_SLOTS = 16 * 1024        # kShCR * kShThreads, gcs_assoc.hip:47 (row capacity ROW_SLOTS // KM, :2257)
+SH_THREADS_X3 = 3 * 512      # k_as_sinkhorn<8, 3> serves n <= 3 * kShThreads, gcs_assoc.hip:46, :2534
+POOL_LDS_MAX_VIEW = 9216     # kPoolLdsMaxView, gcs_assoc.hip:567: lds_slots = 0 past it (:2509)
+LDS_TILES = 256              # kLdsTiles, gcs_assoc.hip:264 (k_as_prep's tile table) = kFusedTiles, :697
+MAX_BUCKETS = 4096           # kMaxBuckets, gcs_assoc.hip:568: n_tiles + 1 > 4096 leaves the bucketed pool (:2462)
 TIE_GAP = 1e-9               # smallest relative gap between different pool costs a case may hold
 
 SMALL = dict(n_feat=64, n_surfel=128, n_valid_cam=40, n_valid_lidar=100, m_tile=64, m_tile_view=64, fill=(0, 50))

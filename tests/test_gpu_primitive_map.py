@@ -264,7 +264,7 @@ def test_map_update_edge_cases(case):
     inserted mass, cull / forget still run), a ragged last association block (N = 301, block 128), a zero
     insert budget, tiles already holding primitives (retention evictions on insert, merges), an
     empty active-tile list (exact no-op), and every candidate on three slots per tile (runs of ~100 rows
-    per (tile, slot, block): k_pm_fuse_chunks cuts them into chunk sums, at the step-12b bar)."""
+    per (tile, slot, block): k_pm_fuse_runs sums each run by one wave, at the step-12b bar)."""
     from types import SimpleNamespace
     from gcslam import primitive_map as gpm
     from oracle import se3
@@ -466,7 +466,7 @@ def test_full_sort_path_matches_oracle():
 
 
 def test_topk_tree_handoff_stress():
-    """The tree top-k's run hand-off between workgroups (k_pm_topk, GCS_TOPK_SC1: write-through stores,
+    """The tree top-k's run hand-off between workgroups (k_pm_topk: write-through stores,
     a relaxed ticket and one acquire by the second arrival; cdna_hip_programming.md Guideline 16) under
     repetition: 24 views of seven dense 50,000-slot tiles with fresh weights each time (ties included),
     every candidate slot against the oracle's stable top-k (primitive_map.py:303-322).  A stale run
