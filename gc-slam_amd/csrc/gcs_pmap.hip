@@ -21,6 +21,9 @@
 //                  (:1907-1930), max_pairs rounds of a (distance, pair index) argmin over eligible pairs
 //                  -- the greedy walk of the stable argsort (:1554-1585) -- then the moment-matched
 //                  merges of the selected (disjoint) pairs (:1603-1707)
+//   export         gcs_pmap_export (end of this file): the variable-length views of the listed tiles,
+//                  concatenated or newest first, as renderable rows and PointCloud2 records
+//                  (map_publisher.py:131-242, backend_node.py:2371-2459)
 // No floating-point atomics; every sum has a fixed order.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -2060,6 +2063,7 @@ struct gcs_pmap {
   uint32_t* topk_skip = nullptr;  // k_pm_topk_sparse -> k_pm_topk: the tiles it finished (max_tiles)
   uint32_t* other_bm = nullptr;   // k_pm_keys -> k_pm_topk_sparse: non-empty-key bitmap (max_tiles x M bits)
   uint32_t* below = nullptr;      // k_pm_keys -> k_pm_topk_sparse: per tile, keys under the empty-slot key
+  int32_t* xp = nullptr;  // gcs_pmap_export: counts, rows, offsets, flag, per-block counts (first call)
   // small host-mapped results
   char* h_small = nullptr;
   char* d_small = nullptr;
@@ -2322,7 +2326,7 @@ int gcs_pmap_destroy(gcs_pmap* p) {
     if (f) (void)hipFree(f);
   void* bufs[] = {p->keys, p->keys_s, p->vals, p->vals_s, p->seg, p->d_tiles, p->d_tids, p->temp, p->fk, p->fk_s,
                   p->fv, p->fv_s, p->ftemp, p->mark, p->dcnt, p->bmark, p->bcnt, p->bticket, p->mmu, p->msig, p->mdet, p->mdist, p->mpd, p->mpp, p->mused,
-                  p->msel, p->mnsel, p->ub, p->run_key, p->run_slot, p->tickets, p->fterm, p->flen, p->topk_skip, p->other_bm, p->below};
+                  p->msel, p->mnsel, p->ub, p->run_key, p->run_slot, p->tickets, p->fterm, p->flen, p->topk_skip, p->other_bm, p->below, p->xp};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (p->h_small) (void)hipHostFree(p->h_small);
@@ -2995,3 +2999,281 @@ int pmap_update_collect(gcs_pmap* p, int64_t* next_global_id, gcs_pmap_update_st
 }
 }  // namespace live
 }  // namespace gcs
+
+// ---------------------------------------------------------------- map publishing and the splat export
+// gcs_pmap_export: the variable-length extract_primitive_map_view (:501-577) of every listed tile the map
+// holds, concatenated (map_publisher.py:146-161), optionally ordered newest first (:198-205), as the
+// renderable batch's rows (:580-616), the export's slot-local fields (backend_node.py:2406-2414) and the
+// packed PointCloud2 records (map_publisher.py:77-86):
+//   k_pmx_count    grid (1,024-slot blocks, tiles): the block's valid slots by ballot / popcount
+//   k_pmx_offsets  one workgroup: per tile the exclusive prefix of its block counts (in place), its
+//                  count and row count min(count, max_primitives); the exclusive prefix of the row counts
+//                  over the tile list (1,024 tiles a pass, carried) and the total
+//   k_pmx_compact  grid as k_pmx_count: row -> (tile position x M + slot); a tile within max_primitives in
+//                  slot order (block prefix + waves before + lanes before: a fixed place, no arrival
+//                  order), a tile over it from the first max_primitives of sort_tiles' mode-0 order
+//   k_pmx_keys     order 1: a row's primitive id, then its negated recency, as order-preserving u64;
+//                  two stable radix sorts, minor key first
+//   k_pmx_rows     one lane per output row in the final order: k_pm_view's arithmetic for position,
+//                  covariance, direction and kappa, Lambda_world by a second LU, copies, the record
+namespace gcs {
+namespace {
+
+struct PmExportOut {
+  double *pos, *cov, *dir, *kap, *lw, *w, *eta, *col, *ts, *cts, *cam, *lid, *acc, *den;
+  int64_t *ids, *lsup, *tid;
+  int32_t* slots;
+  float4* pts;
+};
+
+__global__ __launch_bounds__(kPmRed) void k_pmx_count(PmStore st, const int32_t* tiles, int nbt, int check_min,
+                                                       int32_t* bcnt, int32_t* bad) {
+  __shared__ int s_w[kPmRed / 64];
+  const int t = blockIdx.y, b = blockIdx.x, q = b * kPmRed + threadIdx.x;
+  const int ti = tiles[t];
+  bool v = false;
+  if (ti >= 0 && q < st.M) {
+    const size_t i = sidx(st, ti, q);
+    v = st.valid[i] != 0;
+    if (v && check_min && st.lsup[i] == INT64_MIN) *bad = 1;  // (every writer stores the same value)
+  }
+  const uint64_t m = __ballot(v);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0;
+    for (int w = 0; w < kPmRed / 64; ++w) c += s_w[w];
+    bcnt[(size_t)t * nbt + b] = c;
+  }
+}
+
+__global__ __launch_bounds__(kPmRed) void k_pmx_offsets(int32_t* bcnt, int n, int nbt, int maxp, int32_t* cnt,
+                                                         int32_t* rows, int32_t* off) {
+  __shared__ int s[kPmRed];
+  __shared__ int s_carry;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_carry = 0;
+  __syncthreads();
+  for (int base = 0; base < n; base += kPmRed) {
+    const int t = base + tid;
+    int r = 0;
+    if (t < n) {
+      int c = 0;
+      for (int b = 0; b < nbt; ++b) {
+        const int x = bcnt[(size_t)t * nbt + b];
+        bcnt[(size_t)t * nbt + b] = c;
+        c += x;
+      }
+      cnt[t] = c;
+      r = maxp > 0 && c > maxp ? maxp : c;
+      rows[t] = r;
+    }
+    s[tid] = r;
+    __syncthreads();
+    for (int d = 1; d < kPmRed; d <<= 1) {  // inclusive scan of this pass's row counts
+      const int v = tid >= d ? s[tid - d] : 0;
+      __syncthreads();
+      s[tid] += v;
+      __syncthreads();
+    }
+    const int carry = s_carry;
+    if (t < n) off[t] = carry + s[tid] - r;
+    __syncthreads();
+    if (tid == kPmRed - 1) s_carry = carry + s[tid];
+    __syncthreads();
+  }
+  if (tid == 0) off[n] = s_carry;
+}
+
+__global__ __launch_bounds__(kPmRed) void k_pmx_compact(PmStore st, const int32_t* tiles, int nbt, const int32_t* bpre,
+                                                         const int32_t* cnt, const int32_t* rows, const int32_t* off,
+                                                         const uint32_t* sorted, uint32_t* src) {
+  __shared__ int s_w[kPmRed / 64];
+  const int t = blockIdx.y, b = blockIdx.x, q = b * kPmRed + threadIdx.x;
+  const int ti = tiles[t];
+  if (ti < 0) return;  // (the whole workgroup)
+  const int r = rows[t], o = off[t];
+  if (r < cnt[t]) {  // over max_primitives: the first r of the stable -weight order
+    if (q < r) src[o + q] = sorted[(size_t)t * st.M + q];
+    return;
+  }
+  const bool v = q < st.M && st.valid[sidx(st, ti, q)] != 0;
+  const uint64_t m = __ballot(v);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) s_w[wid] = __popcll(m);
+  __syncthreads();
+  int at = bpre[(size_t)t * nbt + b];
+  for (int w = 0; w < wid; ++w) at += s_w[w];
+  if (v) src[o + at + __popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)t * (uint32_t)st.M + (uint32_t)q;
+}
+
+// which 0: the primitive id, 1: the negated recency (never INT64_MIN: k_pmx_count's flag) -- signed order as u64
+__global__ __launch_bounds__(kPmThreads) void k_pmx_keys(PmStore st, const int32_t* tiles, const uint32_t* src,
+                                                          int nrows, int which, uint64_t* keys) {
+  const int g = blockIdx.x * kPmThreads + threadIdx.x;
+  if (g >= nrows) return;
+  const uint32_t s = src[g];
+  const size_t i = sidx(st, tiles[s / (uint32_t)st.M], (int)(s % (uint32_t)st.M));
+  const uint64_t v = which == 0 ? (uint64_t)st.ids[i] : 0ull - (uint64_t)st.lsup[i];
+  keys[g] = v ^ (1ull << 63);
+}
+
+__global__ __launch_bounds__(kPmThreads) void k_pmx_rows(PmStore st, const int32_t* tiles, const int64_t* tile_ids,
+                                                          const uint32_t* src, int nrows, double eps_lift,
+                                                          double eps_mass, PmExportOut o) {
+#pragma clang fp contract(off)
+  const int g = blockIdx.x * kPmThreads + threadIdx.x;
+  if (g >= nrows) return;
+  const uint32_t s = src[g];
+  const int t = (int)(s / (uint32_t)st.M), q = (int)(s % (uint32_t)st.M);
+  const size_t i = sidx(st, tiles[t], q);
+  constexpr int ne = 3 * kNL;
+  double L[9], th[3], es[3] = {0.0, 0.0, 0.0};
+  for (int c = 0; c < 9; ++c) L[c] = st.lam[9 * i + c];
+  for (int c = 0; c < 3; ++c) th[c] = st.th[3 * i + c];
+  for (int b = 0; b < kNL; ++b)
+    for (int c = 0; c < 3; ++c) {
+      const double e = st.eta[(size_t)ne * i + 3 * b + c];
+      es[c] = b == 0 ? e : es[c] + e;
+      if (o.eta) o.eta[(size_t)ne * g + 3 * b + c] = e;
+    }
+  const double w = st.w[i];
+  double a[3][3], det;
+  int perm[3];
+  lu3(L, eps_lift, a, perm, det);
+  double mu[3];
+  lu3_solve(a, perm, th, mu);
+  if (o.pos)
+    for (int c = 0; c < 3; ++c) o.pos[3 * (size_t)g + c] = mu[c];
+  if (o.cov || o.lw) {
+    double S[9];
+    lu3_inv(a, perm, S);
+    if (o.cov)
+      for (int c = 0; c < 9; ++c) o.cov[9 * (size_t)g + c] = S[c];
+    if (o.lw) {
+      double W[9];
+      lu3(S, eps_lift, a, perm, det);
+      lu3_inv(a, perm, W);
+      for (int c = 0; c < 9; ++c) o.lw[9 * (size_t)g + c] = W[c];
+    }
+  }
+  const double kap = sqrt((es[0] * es[0] + es[1] * es[1]) + es[2] * es[2]);
+  if (o.dir)
+    for (int c = 0; c < 3; ++c) o.dir[3 * (size_t)g + c] = es[c] / (kap + eps_mass);
+  if (o.kap) o.kap[g] = kap;
+  if (o.w) o.w[g] = w;
+  for (int c = 0; c < 3; ++c) {
+    if (o.col) o.col[3 * (size_t)g + c] = st.rgb[3 * i + c];
+    if (o.acc) o.acc[3 * (size_t)g + c] = st.acc[3 * i + c];
+  }
+  if (o.ids) o.ids[g] = st.ids[i];
+  if (o.lsup) o.lsup[g] = st.lsup[i];
+  if (o.tid) o.tid[g] = tile_ids[t];
+  if (o.slots) o.slots[g] = q;
+  if (o.ts) o.ts[g] = st.ts[i];
+  if (o.cts) o.cts[g] = st.cts[i];
+  if (o.cam) o.cam[g] = st.cam[i];
+  if (o.lid) o.lid[g] = st.lid[i];
+  if (o.den) o.den[g] = st.den[i];
+  if (o.pts) {
+    // astype(float32) (round to nearest even, +-inf out of range), then np.clip in float32: NaN stays
+    // NaN, and -0.0 stays -0.0 (numpy's clip keeps x where x >= lo)
+    const float wf = (float)w;
+    float inten = wf;
+    if (wf == wf) {
+      inten = wf >= 0.0f ? wf : 0.0f;
+      inten = inten <= 1e6f ? inten : 1e6f;
+    }
+    o.pts[g] = make_float4((float)mu[0], (float)mu[1], (float)mu[2], inten);  // one 16-byte store
+  }
+}
+
+}  // namespace
+}  // namespace gcs
+
+extern "C" {
+
+int gcs_pmap_export(gcs_pmap* p, const int32_t* tiles, const int64_t* tile_ids, int32_t n, int32_t max_primitives,
+                    int32_t order, double eps_lift, double eps_mass, int32_t capacity, const gcs_pmap_export_out* o,
+                    int32_t* n_rows, int32_t* tile_rows) {
+  if (!p || !o || !n_rows) return GCS_ERR_ARG;
+  *n_rows = 0;
+  if (n > 0 && !tile_ids) return pm_fail(p, GCS_ERR_ARG, "export: null tile ids");
+  if (max_primitives < 0 || capacity < 0) return pm_fail(p, GCS_ERR_ARG, "export: negative max_primitives or capacity");
+  if (order != GCS_PM_ORDER_CONCAT && order != GCS_PM_ORDER_RECENCY)
+    return pm_fail(p, GCS_ERR_ARG, "export: order must be 0 (concatenation) or 1 (recency)");
+  if (((uintptr_t)o->points & 15) != 0) return pm_fail(p, GCS_ERR_ARG, "export: points must be 16-byte aligned");
+  if (int rc = check_tiles(p, tiles, n, true)) return rc;
+  if (n > 65535) return pm_fail(p, GCS_ERR_ARG, "export: more than 65,535 listed tiles");
+  if (n == 0) return GCS_OK;
+  PMCHK(p, hipSetDevice(p->device));
+  const int T = p->T, nbt = (p->M + kPmRed - 1) / kPmRed;
+  const size_t head = 3 * (size_t)T + 2;  // counts T | rows T | offsets T + 1 | flag
+  if (!p->xp) PMCHK(p, hipMalloc(&p->xp, (head + (size_t)T * nbt) * sizeof(int32_t)));
+  int32_t *cnt = p->xp, *rows = p->xp + T, *off = p->xp + 2 * (size_t)T, *bad = p->xp + 3 * (size_t)T + 1,
+          *bcnt = p->xp + head;
+  if (int rc = upload_tiles(p, tiles, n)) return rc;
+  PMCHK(p, hipMemcpyAsync(p->d_tids, tile_ids, n * sizeof(int64_t), hipMemcpyHostToDevice, p->stream));
+  PMCHK(p, hipMemsetAsync(bad, 0, sizeof(int32_t), p->stream));
+  hipLaunchKernelGGL(k_pmx_count, dim3(nbt, n), dim3(kPmRed), 0, p->stream, p->st, (const int32_t*)p->d_tiles, nbt,
+                     order == GCS_PM_ORDER_RECENCY ? 1 : 0, bcnt, bad);
+  hipLaunchKernelGGL(k_pmx_offsets, dim3(1), dim3(kPmRed), 0, p->stream, bcnt, n, nbt, max_primitives, cnt, rows, off);
+  PMCHK(p, hipGetLastError());
+  std::vector<int32_t> h(head);
+  PMCHK(p, hipMemcpyAsync(h.data(), p->xp, head * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+  PMCHK(p, hipStreamSynchronize(p->stream));
+  const int total = h[2 * (size_t)T + n];
+  *n_rows = total;
+  bool down = false;
+  for (int t = 0; t < n; ++t) {
+    if (tile_rows) tile_rows[t] = h[T + t];
+    down = down || h[T + t] < h[t];
+  }
+  if (h[3 * (size_t)T + 1])
+    return pm_fail(p, GCS_ERR_ARG, "export: a last_supported_scan_seq of INT64_MIN cannot be negated for the recency order");
+  if (total > capacity) return pm_fail(p, GCS_ERR_ARG, "export: the rows exceed capacity (n_rows holds the count)");
+  if (total == 0) return GCS_OK;
+  if (down)  // per tile the stable -weight order's first max_primitives (tile position x M + slot in vals)
+    if (int rc = sort_tiles(p, n, 0, 0, 0.0, max_primitives)) return rc;
+  hipLaunchKernelGGL(k_pmx_compact, dim3(nbt, n), dim3(kPmRed), 0, p->stream, p->st, (const int32_t*)p->d_tiles, nbt,
+                     (const int32_t*)bcnt, (const int32_t*)cnt, (const int32_t*)rows, (const int32_t*)off,
+                     (const uint32_t*)p->vals, p->seg);
+  const uint32_t* fin = p->seg;
+  const unsigned gb = (unsigned)((total + kPmThreads - 1) / kPmThreads);
+  if (order == GCS_PM_ORDER_RECENCY && total > 1) {
+    // np.lexsort((ids, -recency)): stable on the id, then stable on the negated recency
+    size_t tb = 0;  // (rocPRIM's path, and with it its scratch, depends on the row count)
+    PMCHK(p, rocprim::radix_sort_pairs(nullptr, tb, p->keys, p->keys_s, p->seg, p->vals_s, (unsigned)total, 0u, 64u,
+                                       p->stream));
+    if (tb > p->temp_bytes) {
+      PMCHK(p, hipStreamSynchronize(p->stream));
+      PMCHK(p, hipFree(p->temp));
+      p->temp = nullptr;
+      p->temp_bytes = 0;
+      PMCHK(p, hipMalloc(&p->temp, tb));
+      p->temp_bytes = tb;
+    }
+    tb = p->temp_bytes;
+    hipLaunchKernelGGL(k_pmx_keys, dim3(gb), dim3(kPmThreads), 0, p->stream, p->st, (const int32_t*)p->d_tiles,
+                       (const uint32_t*)p->seg, total, 0, p->keys);
+    PMCHK(p, rocprim::radix_sort_pairs(p->temp, tb, p->keys, p->keys_s, p->seg, p->vals_s, (unsigned)total, 0u, 64u,
+                                       p->stream));
+    hipLaunchKernelGGL(k_pmx_keys, dim3(gb), dim3(kPmThreads), 0, p->stream, p->st, (const int32_t*)p->d_tiles,
+                       (const uint32_t*)p->vals_s, total, 1, p->keys);
+    tb = p->temp_bytes;
+    PMCHK(p, rocprim::radix_sort_pairs(p->temp, tb, p->keys, p->keys_s, p->vals_s, p->vals, (unsigned)total, 0u, 64u,
+                                       p->stream));
+    fin = p->vals;
+  }
+  PmExportOut x{o->positions, o->covariances, o->directions, o->kappas, o->lambda_world, o->weights, o->etas,
+                o->colors, o->timestamps, o->created_timestamps, o->cam_mass, o->lidar_mass, o->rgb_cam_accum,
+                o->rgb_cam_denom, o->primitive_ids, o->last_supported_scan_seq, o->tile_ids, o->slots,
+                (float4*)o->points};
+  hipLaunchKernelGGL(k_pmx_rows, dim3(gb), dim3(kPmThreads), 0, p->stream, p->st, (const int32_t*)p->d_tiles,
+                     (const int64_t*)p->d_tids, fin, total, eps_lift, eps_mass, x);
+  PMCHK(p, hipGetLastError());
+  PMCHK(p, hipStreamSynchronize(p->stream));
+  return GCS_OK;
+}
+
+}  // extern "C"

@@ -224,6 +224,13 @@ class GcsPmapView(C.Structure):
                                           "candidate_slots", "candidate_tile_ids")]
 
 
+class GcsPmapExportOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("positions", "covariances", "directions", "kappas", "lambda_world", "weights",
+                                          "etas", "colors", "primitive_ids", "last_supported_scan_seq", "tile_ids",
+                                          "slots", "timestamps", "created_timestamps", "cam_mass", "lidar_mass",
+                                          "rgb_cam_accum", "rgb_cam_denom", "points")]
+
+
 class GcsPmapRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("Lambdas", "thetas", "etas", "weights", "responsibilities", "valid",
                                           "colors", "sources", "tile_pos", "slots")] + [("n", C.c_int32)]
@@ -457,6 +464,8 @@ _SIGS = [
     ("gcs_pmap_map_update", C.c_int, [C.c_void_p, c_int32_p, c_int64_p, C.c_int32, c_double_p, C.c_double, C.c_int64,
                                       c_int64_p, C.POINTER(GcsPmapUpdateConfig), C.POINTER(GcsPmapUpdateInputs),
                                       C.POINTER(GcsPmapUpdateStats), c_int32_p]),
+    ("gcs_pmap_export", C.c_int, [C.c_void_p, c_int32_p, c_int64_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                  C.c_double, C.c_int32, C.POINTER(GcsPmapExportOut), c_int32_p, c_int32_p]),
     ("gcs_live_scan", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GcsScanBeginOutputs), C.POINTER(GcsLiveArgs),
                                 C.POINTER(GcsLiveOutputs), C.POINTER(GcsScanOutputs)]),
     ("gcs_live_collect", C.c_int, [C.c_void_p, C.POINTER(GcsLiveOutputs)]),

@@ -989,6 +989,44 @@ int gcs_pmap_recency_inflate(gcs_pmap* pm, const int32_t* tiles, int32_t n, int6
 int gcs_pmap_merge_reduce(gcs_pmap* pm, int32_t tile, double merge_threshold, int32_t max_pairs, double eps_psd,
                           double eps_lift, int32_t* n_merged, int32_t* pairs, int32_t* count);
 
+/* Map publishing and the splat export (FS/backend/map_publisher.py:131-242, backend_node.py:2371-2459):
+ * the variable-length extract_primitive_map_view (primitive_map.py:501-577) of each listed tile,
+ * concatenated in list order, optionally ordered newest first, as renderable rows and packed
+ * PointCloud2 records.  Device pointers to `capacity` rows each; any may be NULL. */
+typedef struct {
+  double* positions;        /* x 3 */
+  double* covariances;      /* x 9 */
+  double* directions;       /* x 3 */
+  double* kappas;
+  double* lambda_world;     /* x 9: inv(covariance + eps_lift I), renderable_batch_from_view (:600-607) */
+  double* weights;
+  double* etas;             /* x n_lobes*3 */
+  double* colors;           /* x 3 (the tile's rgb) */
+  int64_t* primitive_ids;
+  int64_t* last_supported_scan_seq;
+  int64_t* tile_ids;        /* the row's source tile id */
+  int32_t* slots;           /* ... and slot */
+  double* timestamps;       /* the slot-local fields of the splat export */
+  double* created_timestamps;
+  double* cam_mass;
+  double* lidar_mass;
+  double* rgb_cam_accum;    /* x 3 */
+  double* rgb_cam_denom;
+  void* points;             /* 16-byte records x, y, z, intensity (float32); 16-byte aligned */
+} gcs_pmap_export_out;
+enum { GCS_PM_ORDER_CONCAT = 0, GCS_PM_ORDER_RECENCY = 1 };
+/* tiles / tile_ids: n host storage indices and ids in list order; a tile the map lacks (-1) is skipped
+ * (map_publisher.py:149-151), an id listed twice contributes twice.  Per tile the valid slots in slot
+ * order, or, where max_primitives > 0 and the tile's valid count exceeds it, the first max_primitives of
+ * the stable order of -weight (:541-545).  order 0: concatenation order; order 1: stable by
+ * (-last_supported_scan_seq, primitive_id) over all 64 bits, np.lexsort((ids, -recency)); a valid slot
+ * of a listed tile with recency INT64_MIN is refused (GCS_ERR_ARG: its negation overflows).
+ * n_rows (host): the total row count; tile_rows (host, n; may be NULL): rows per listed tile.  If
+ * n_rows exceeds capacity the call returns GCS_ERR_ARG with n_rows and tile_rows set and writes no row. */
+int gcs_pmap_export(gcs_pmap* pm, const int32_t* tiles, const int64_t* tile_ids, int32_t n, int32_t max_primitives,
+                    int32_t order, double eps_lift, double eps_mass, int32_t capacity, const gcs_pmap_export_out* out,
+                    int32_t* n_rows, int32_t* tile_rows);
+
 /* Step 12b of process_scan_single_hypothesis (pipeline.py:1232-1492): the map update at z_t from the
  * scan's MeasurementBatch and PrimitiveAssociationResult over the n active tiles (storage indices +
  * MA-hex ids, the association stencil's tiles): per association block (block_associations_for_fuse,
