@@ -162,6 +162,43 @@ class GcsCamsplatOutputs(C.Structure):
                [("n_camera_valid", C.c_int32)]
 
 
+VF_NEAREST, VF_MEDIAN3, VF_MEDIAN5, VF_HEX = 0, 1, 2, 3
+VF_DEPTH_LINEAR, VF_DEPTH_QUADRATIC = 0, 1
+VISFEAT_CONFIG_DOUBLES = ("pixel_sigma", "depth_sigma0", "depth_sigma_slope", "min_depth_m", "max_depth_m",
+                          "depth_validity_slope", "response_soft_scale", "depth_scale", "cov_reg_eps",
+                          "invalid_cov_inflate", "quad_fit_lstsq_eps", "student_t_nu", "student_t_w_min", "ma_tau",
+                          "ma_delta_inflate", "kappa0", "kappa_alpha", "kappa_max", "kappa_min")
+
+
+class GcsVisfeatConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("max_features", "depth_sample_mode", "depth_model", "hex_radius",
+                                         "quad_fit_radius", "quad_fit_min_points")] + \
+               [(n, C.c_double) for n in VISFEAT_CONFIG_DOUBLES] + \
+               [("max_keypoints", C.c_int32), ("device", C.c_int32)]
+
+
+class GcsVisfeatInputs(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("depth_format", C.c_int32), ("depth_pitch", C.c_int64),
+                ("width", C.c_int32), ("height", C.c_int32), ("rgb", C.c_void_p), ("rgb_pitch", C.c_int64),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("n_keypoints", C.c_int32), ("kp_u", C.c_void_p), ("kp_v", C.c_void_p), ("kp_response", C.c_void_p)]
+
+
+# (name, row width, dtype name) of gcs_visfeat_outputs' arrays: the twelve feature arrays, then the diagnostics
+VISFEAT_FEATURE_FIELDS = (("u", 0, "float64"), ("v", 0, "float64"), ("xyz", 3, "float64"), ("cov", 9, "float64"),
+                          ("weight", 0, "float64"), ("kappa_app", 0, "float64"), ("mu_app", 3, "float64"),
+                          ("has_mu", 0, "uint8"), ("color", 3, "float64"), ("has_color", 0, "uint8"),
+                          ("depth_Lambda_c", 0, "float64"), ("depth_theta_c", 0, "float64"))
+VISFEAT_DIAG_FIELDS = (("kp_index", 0, "int32"), ("z_valid", 0, "uint8"), ("n_depth", 0, "int32"),
+                       ("n_fit", 0, "int32"), ("z_m", 0, "float64"), ("z_var", 0, "float64"),
+                       ("var_z_eff", 0, "float64"), ("beta", 6, "float64"), ("K", 0, "float64"),
+                       ("lam_min", 0, "float64"), ("w_ma", 0, "float64"))
+
+
+class GcsVisfeatOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n, _, _ in VISFEAT_FEATURE_FIELDS + VISFEAT_DIAG_FIELDS] + [("count", C.c_int32)]
+
+
 class GcsRenderConfig(C.Structure):
     _fields_ = [("tile_size", C.c_int32), ("max_splats_per_tile", C.c_int32), ("fbm_octaves", C.c_int32),
                 ("fbm_gain", C.c_double), ("opacity_gamma", C.c_double), ("logdet0", C.c_double), ("eps", C.c_double),
@@ -414,6 +451,14 @@ _SIGS = [
     ("gcs_camera_splats", C.c_int, [C.c_void_p, C.POINTER(GcsCamsplatInputs), C.POINTER(GcsCamsplatOutputs)]),
     ("gcs_camera_splats_scan", C.c_int, [C.c_void_p, C.POINTER(GcsCamsplatInputs), C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_int32, C.POINTER(GcsCamsplatOutputs)]),
+    ("gcs_visfeat_config_defaults", C.c_int, [C.POINTER(GcsVisfeatConfig)]),
+    ("gcs_visfeat_ctx_create", C.c_int, [C.POINTER(GcsVisfeatConfig), C.POINTER(C.c_void_p)]),
+    ("gcs_visfeat_ctx_destroy", C.c_int, [C.c_void_p]),
+    ("gcs_visfeat_last_error", C.c_char_p, [C.c_void_p]),
+    ("gcs_visfeat_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gcs_visual_features", C.c_int, [C.c_void_p, C.POINTER(GcsVisfeatInputs), C.POINTER(GcsVisfeatOutputs)]),
+    ("gcs_visual_features_host", C.c_int, [C.POINTER(GcsVisfeatConfig), C.POINTER(GcsVisfeatInputs),
+                                           C.POINTER(GcsVisfeatOutputs)]),
     ("gcs_render_config_defaults", C.c_int, [C.POINTER(GcsRenderConfig)]),
     ("gcs_render_ctx_create", C.c_int, [C.POINTER(GcsRenderConfig), C.POINTER(C.c_void_p)]),
     ("gcs_render_ctx_destroy", C.c_int, [C.c_void_p]),

@@ -217,8 +217,13 @@ class CameraSplatBuilder:
             diag = self.diag_tensors(int(i.n_features))
             for k, x in diag.items():
                 setattr(o, k, x.data_ptr())
-        self._chk(self.lib.gcs_camsplat_ctx_set_stream(self.h, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                  "gcs_camsplat_ctx_set_stream")
+        ts = torch.cuda.current_stream(dev)
+        self._chk(self.lib.gcs_camsplat_ctx_set_stream(self.h, C.c_void_p(ts.cuda_stream)), "gcs_camsplat_ctx_set_stream")
+        if not ts.cuda_stream:
+            # torch's default stream is handle 0, for which the context queues on a stream of its own that the
+            # default stream does not order: what produced the features and points there (an upload, or
+            # gcs_visual_features, which does not wait) has to be complete first
+            ts.synchronize()
         if records is None:
             i.points_base, i.n_points = points.data_ptr(), int(points.shape[0])
             self._chk(self.lib.gcs_camera_splats(self.h, C.byref(i), C.byref(o)), "gcs_camera_splats")
@@ -303,7 +308,9 @@ def _builder_for(config, n_feat, n_surfel, eps_lift, n_points, device, max_candi
 @dataclass
 class CameraFrame:
     """One scan's visual features as the node holds them ahead of its hypothesis loop
-    (backend_node.py:1834-1925): the feature set (see feature_arrays), the pinhole intrinsics, the camera's
+    (backend_node.py:1834-1925): the feature set (see feature_arrays; or device features, as
+    CameraSplatBuilder.device_features and gcslam.visual.extract_visual_features return them, which are
+    used where they are with no host copy), the pinhole intrinsics, the camera's
     pose in the base frame (p_base = R p_camera + t), the batch's timestamp and the depth-fusion config.
     process_scan_single_hypothesis(camera_batch=CameraFrame(...), camera_batch_policy="use") builds the
     batch's camera slice from the scan's own points inside the scan (the node's splat_prep_fused reads the
@@ -339,17 +346,39 @@ class CameraFrame:
             raise ValueError("CameraFrame.timestamp_sec is not finite")
         if not 1 <= int(self.max_candidates) <= 1024:
             raise ValueError("CameraFrame.max_candidates outside [1, 1024]")
-        self.arrays = feature_arrays(self.features)   # host arrays, validated once
+        # host arrays, validated once -- or device features (CameraSplatBuilder.device_features,
+        # gcslam.visual.extract_visual_features), which stay where they are: arrays is then None
+        on_device = getattr(self.features, "_on_device", False)
+        self.device_arrays = self.features if on_device else None
+        self.arrays = None if on_device else feature_arrays(self.features)
+        held = self.device_arrays if on_device else self.arrays
         m = self.n_features
         if m > 65535:
             raise ValueError("CameraFrame: more than 65535 features")
-        for name, w in _FEATURE_ARRAYS:
-            if self.arrays[name].shape != ((m, w) if w else (m,)):
-                raise ValueError(f"CameraFrame.features[{name!r}]: shape {self.arrays[name].shape}")
+        for name, w in _FEATURE_ARRAYS + ((("has_mu", 0), ("has_color", 0)) if on_device else ()):
+            if name not in held:
+                raise KeyError(f"features: missing array {name!r}")
+            if tuple(held[name].shape) != ((m, w) if w else (m,)):
+                raise ValueError(f"CameraFrame.features[{name!r}]: shape {tuple(held[name].shape)}")
+        if on_device:
+            torch = _torch()
+            for name, w in _FEATURE_ARRAYS + (("has_mu", 0), ("has_color", 0)):
+                x, dt = held[name], (torch.uint8 if name.startswith("has_") else torch.float64)
+                if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dt and x.is_contiguous()):
+                    raise ValueError(f"CameraFrame.features[{name!r}]: a contiguous {dt} device tensor")
 
     @property
     def n_features(self) -> int:
-        return int(self.arrays["u"].shape[0])
+        return int((self.arrays if self.arrays is not None else self.device_arrays)["u"].shape[0])
+
+    def features_on(self, device: int) -> "_DeviceFeatures":
+        """The features on GPU `device`: the frame's own device tensors, or its host arrays uploaded."""
+        if self.device_arrays is None:
+            return _upload_features(self.arrays, device)
+        if self.n_features and self.device_arrays["u"].device.index != int(device):
+            raise ValueError(f"CameraFrame: device features on {self.device_arrays['u'].device}, the scan on "
+                             f"cuda:{int(device)}")
+        return self.device_arrays
 
     @property
     def n_valid(self) -> int:   # (an empty frame is no camera batch: the scan runs LiDAR-only)

@@ -392,7 +392,7 @@ def _process_scan_primitive(ctx: HypothesisContext, primitive_map, belief_prev, 
     if frame is not None:
         # the scan's own point values (the float32 records, widened exactly) through gcs_camera_splats
         b = frame.builder(config.n_feat, config.n_surfel, config.eps_lift, int(rec.shape[0]), config.device)
-        camera_batch = b.build(b.device_features(frame.arrays), rec[:, :3].to(torch.float64), frame.intrinsics,
+        camera_batch = b.build(frame.features_on(config.device), rec[:, :3].to(torch.float64), frame.intrinsics,
                                frame.R_base_camera, frame.t_base_camera, frame.timestamp_sec,
                                want_diag=frame.want_diag)
         camera_diag = getattr(camera_batch, "camera_diag", None)
@@ -702,9 +702,8 @@ def _process_scan_live_chain(ctx: HypothesisContext, primitive_map, rec, t, w, i
             setattr(cam_out, name, base + lay["off"][("batch", name)])
         cam.out = C.addressof(cam_out)
         if hasattr(camera, "arrays"):  # a CameraFrame: form A, on the records the begin reads
-            from .camera import _upload_features
             b = camera.builder(config.n_feat, config.n_surfel, config.eps_lift, int(rec.shape[0]), config.device)
-            fa = _upload_features(camera.arrays, config.device)
+            fa = camera.features_on(config.device)   # device features as they are, host arrays uploaded
             ci = b.inputs_struct(fa, camera.intrinsics, camera.R_base_camera, camera.t_base_camera,
                                  camera.timestamp_sec)
             cam.ctx, cam.inputs = b.h.value, C.addressof(ci)

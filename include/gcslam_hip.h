@@ -39,6 +39,9 @@
  *   gcs_camera_splats           FS/frontend/sensors/lidar_camera_depth_fusion.py + splat_prep.py:37-134
  *                               (lidar_depth_evidence, splat_prep_fused), FS/backend/backend_node.py:
  *                               1872-1925, FS/backend/structures/measurement_batch.py:165-259
+ *   gcs_visual_features         src/visual_feature_node.cpp:228-652 (on_rgbd after ORB: depth_sample,
+ *                               student_t_effective_var, quadratic_fit, backprojection_cov) and
+ *                               FS/backend/backend_node.py:1589-1650 _feature_batch_to_list
  */
 #ifndef GCSLAM_HIP_H
 #define GCSLAM_HIP_H
@@ -685,6 +688,105 @@ int gcs_camera_splats(gcs_camsplat_ctx* ctx, const gcs_camsplat_inputs* in, gcs_
  * are bit for bit those of gcs_camera_splats on the float64 array of the same values. */
 int gcs_camera_splats_scan(gcs_camsplat_ctx* ctx, const gcs_camsplat_inputs* in, const void* xyz_dev,
                            int32_t point_step, int32_t xyz_format, int32_t n_points, gcs_camsplat_outputs* out);
+
+/* ---------------------------------------------------------------- primitive path: visual features */
+/* The visual feature node's per-keypoint numerics (src/visual_feature_node.cpp:493-652 on_rgbd, after
+ * ORB) on the GPU, from a depth image and a keypoint list to the feature arrays gcs_camsplat_inputs
+ * reads: the robust depth sample (:228-348: nearest, median3, median5, hex), the Student-t effective
+ * variance (:350-369, :563-572), the 6-parameter quadratic surface fit with its normal, Gaussian
+ * curvature and smallest Hessian eigenvalue (:401-491), the back-projection and its closed-form
+ * covariance (:371-399), the medial-axis covariance inflation, the vMF kappa, the weights and the
+ * colour (:546-641), and _feature_batch_to_list's renormalised mu_app (backend_node.py:1589-1650).
+ * One wave64 per keypoint, one lane per window pixel, all f64; the median is an input value picked
+ * by rank (element n / 2 of the sorted valid values, ties by lane) and the normal equations are
+ * butterfly sums in a fixed order, so two calls agree bit for bit.  The keypoint detector (ORB) is not
+ * part of the library: kp_u, kp_v, kp_response are cv::KeyPoint's pt.x, pt.y, response.
+ * Declared where the node leaves it open: with n_keypoints > max_features the max_features largest
+ * responses are kept (ties to the lower index, NaN last) and written in input order; a keypoint with
+ * a non-finite u or v, or |u| or |v| > 1e9, is outside the image; a NaN response weighs 0.  A keypoint
+ * without a valid depth still yields a feature (xyz 0, cov invalid_cov_inflate I, weight 0).
+ * Calls on one context must be serialised. */
+typedef struct gcs_visfeat_ctx gcs_visfeat_ctx;
+#define GCS_VF_NEAREST 0
+#define GCS_VF_MEDIAN3 1
+#define GCS_VF_MEDIAN5 2
+#define GCS_VF_HEX 3
+#define GCS_VF_DEPTH_LINEAR 0
+#define GCS_VF_DEPTH_QUADRATIC 1
+
+typedef struct {
+  /* the node's parameters (:70-103), same names and defaults */
+  int32_t max_features;          /* 512: rows of every output array */
+  int32_t depth_sample_mode;     /* GCS_VF_MEDIAN3 */
+  int32_t depth_model;           /* GCS_VF_DEPTH_LINEAR */
+  int32_t hex_radius;            /* 2; below 1 behaves as 1 (:303), at most 32 */
+  int32_t quad_fit_radius;       /* 2; below 1 behaves as 1 (:407), at most 3: (2r + 1)^2 <= 49 lanes */
+  int32_t quad_fit_min_points;   /* 6 */
+  double pixel_sigma, depth_sigma0, depth_sigma_slope, min_depth_m, max_depth_m, depth_validity_slope;
+  double response_soft_scale, depth_scale;
+  double cov_reg_eps;            /* declared by the node, read nowhere in it */
+  double invalid_cov_inflate;
+  double quad_fit_lstsq_eps, student_t_nu, student_t_w_min, ma_tau, ma_delta_inflate;
+  double kappa0, kappa_alpha, kappa_max, kappa_min;
+  int32_t max_keypoints;         /* 4096: capacity of the context (keypoints per call), >= max_features */
+  int32_t device;
+} gcs_visfeat_config;
+
+/* One frame.  Device pointers for gcs_visual_features, host pointers for gcs_visual_features_host. */
+typedef struct {
+  const void* depth;             /* height rows of width values, depth_pitch bytes apart */
+  int32_t depth_format;          /* 0: float32, 1: uint16; metres = value * depth_scale */
+  int64_t depth_pitch;           /* >= width * (4 or 2), a multiple of the value's size */
+  int32_t width, height;
+  const uint8_t* rgb;            /* rgb8, rows rgb_pitch (>= 3 width) bytes apart; NULL: no colour */
+  int64_t rgb_pitch;
+  double fx, fy, cx, cy;         /* camera_K (:103) */
+  int32_t n_keypoints;           /* <= max_keypoints */
+  const float *kp_u, *kp_v, *kp_response;   /* n_keypoints */
+} gcs_visfeat_inputs;
+
+/* Outputs: max_features rows each, rows [count, max_features) zeros (kp_index -1).  The twelve feature
+ * arrays are gcs_camsplat_inputs' arrays; the diagnostics may each be NULL. */
+typedef struct {
+  double *u, *v;                 /* the keypoint's coordinates, widened */
+  double* xyz;                   /* x 3, camera frame */
+  double* cov;                   /* x 9 */
+  double *weight, *kappa_app;
+  double* mu_app;                /* x 3: the fit's normal / (|normal| + 1e-12); zeros without a fit */
+  uint8_t* has_mu;               /* 1 exactly where the fit exists */
+  double* color;                 /* x 3: rgb / 255 at the clamped, rounded (u, v); zeros without an image */
+  uint8_t* has_color;            /* 1 when rgb was given */
+  double *depth_Lambda_c, *depth_theta_c;   /* 1 / var_z_eff and z / var_z_eff (0 without a depth) */
+  /* diagnostics */
+  int32_t* kp_index;             /* the keypoint each row came from */
+  uint8_t* z_valid;
+  int32_t* n_depth;              /* valid values in the depth sample */
+  int32_t* n_fit;                /* valid pixels in the fit window (0 where the depth is invalid) */
+  double* z_m;                   /* the sampled depth (NaN where invalid) */
+  double* z_var;                 /* the sample's own variance, NaN where the node has none */
+  double* var_z_eff;
+  double* beta;                  /* x 6: the fit's coefficients (NaN without a fit, as K, lam_min, w_ma) */
+  double *K, *lam_min, *w_ma;
+  /* host result */
+  int32_t count;                 /* min(n_keypoints, max_features) */
+} gcs_visfeat_outputs;
+
+int gcs_visfeat_config_defaults(gcs_visfeat_config* cfg);
+/* GCS_ERR_ARG, before any device call, for quad_fit_radius > 3, hex_radius > 32, max_features < 1,
+ * max_keypoints < max_features or an unknown depth_sample_mode / depth_model. */
+int gcs_visfeat_ctx_create(const gcs_visfeat_config* cfg, gcs_visfeat_ctx** out);
+int gcs_visfeat_ctx_destroy(gcs_visfeat_ctx* ctx);
+const char* gcs_visfeat_last_error(const gcs_visfeat_ctx* ctx);
+/* stream: a hipStream_t, NULL being HIP's default stream, which is also what a new context queues on (the
+ * call does not synchronise, so unlike the contexts above this one has no stream of its own to hide behind:
+ * the work is ordered with the caller's work on the stream it names) */
+int gcs_visfeat_ctx_set_stream(gcs_visfeat_ctx* ctx, void* stream);
+/* Queues its kernels on the context's stream and returns: count is known on the host, nothing is waited
+ * for.  The arrays are ready for work queued later on the same stream. */
+int gcs_visual_features(gcs_visfeat_ctx* ctx, const gcs_visfeat_inputs* in, gcs_visfeat_outputs* out);
+/* The same rows on the host (no device, no context): every pointer is a host array. */
+int gcs_visual_features_host(const gcs_visfeat_config* cfg, const gcs_visfeat_inputs* in,
+                             gcs_visfeat_outputs* out);
 
 /* ---------------------------------------------------------------- primitive path: map rendering */
 /* The reference's output side (backend/rendering.py, common/bev_pushforward.py) on the GPU, reading
