@@ -14,7 +14,7 @@ torch = pytest.importorskip("torch")
 from golden_util import load
 from gcslam import synthetic
 from oracle import se3
-from test_imu_odom import TOL, _inputs, _oracle
+from test_imu_odom import _compare, _inputs, _oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -42,18 +42,7 @@ def _device(ctx, d):
 
 
 def _check(ctx, d):
-    L_o, h_o, named, info, dt_int, dt_imu, om = _oracle(d)
-    L_d, h_d, cert = _device(ctx, d)
-    sc = np.abs(L_o).max()
-    np.testing.assert_allclose(L_d, L_o, rtol=1e-9, atol=1e-12 * sc)
-    np.testing.assert_allclose(h_d, h_o, rtol=1e-9, atol=1e-12 * max(np.abs(h_o).max(), 1.0))
-    np.testing.assert_allclose(cert[0], info["trigger"], rtol=1e-9)
-    np.testing.assert_allclose(cert[1:7], [info["ess_weighted"], info["kappa"], info["transport_sigma"],
-                                           info["imu_scale"], info["odom_scale"], info["mean_reliability"]], **TOL)
-    np.testing.assert_allclose(cert[7:10], [named["odom"]["nll_per_ess"], named["imu"]["nll_per_ess"],
-                                            named["gyro"]["nll_per_ess"]], rtol=1e-8, atol=1e-12)
-    np.testing.assert_allclose(cert[10:15], [dt_int, dt_imu, *om], **TOL)
-    assert np.all(np.isfinite(L_d)) and np.allclose(L_d, L_d.T, atol=1e-9 * sc)
+    _compare(*_device(ctx, d), _oracle(d))  # the host branch's assertions (tests/test_imu_odom.py)
 
 
 def test_device_branch_kimera_windows_match_oracle():
@@ -97,10 +86,8 @@ def test_device_branch_synthetic_windows_match_oracle(seed):
         ctx.close()
 
 
-@pytest.mark.parametrize("mode,B,cap,n", [("dense", 48, 2048, 4096), ("scale", 20000, 8192, 8192)])
-def test_scans_with_device_branch_match_host_branch(mode, B, cap, n):
-    """Three consecutive 14-step scans with the device IMU / odometry branch against the same scans with
-    the host branch: z_t, the belief, the IMU / odometry evidence and its certificates."""
+def _scans_both_branches(scans, mode, B, cap, n):
+    """The scans through one context per branch (the host's, then the device's)."""
     from gcslam import _lib as L
     from gcslam.context import HypothesisContext
     from gcslam.synthetic import scan_kwargs
@@ -110,8 +97,7 @@ def test_scans_with_device_branch_match_host_branch(mode, B, cap, n):
         ctx.set_debug(L.DEBUG_DEVICE_IMU_ODOM, dev)
         out = []
         try:
-            for s in range(3):
-                sc = synthetic.make_scan(n, 120 + s)
+            for sc in scans:
                 rec = torch.from_numpy(sc["xyz_record"]).cuda()
                 t = torch.from_numpy(sc["timestamps"]).cuda()
                 w = torch.from_numpy(sc["weights"]).cuda()
@@ -123,6 +109,10 @@ def test_scans_with_device_branch_match_host_branch(mode, B, cap, n):
         finally:
             ctx.close()
         runs.append(out)
+    return runs
+
+
+def _branch_mismatches(runs):
     # the evidence itself at the device-vs-host bars of the windows above, on every scan; the scan's
     # downstream outputs at the pipeline's multi-scan bar (tests/test_gpu_fullsize.py: rtol 1e-7) on the
     # first two scans, and the pose-6 conditioning (cert[49], an eigenvalue ratio of the summed evidence:
@@ -133,7 +123,8 @@ def test_scans_with_device_branch_match_host_branch(mode, B, cap, n):
     # moved z_t by 1.8e-7 m and single L entries by up to 1.2e-5 of max|L| (profiles/r06/imu_odom/), so
     # that scan's z_t / L take atol 1e-6 m / 1e-4 max|L|.
     bad = []
-    for s in range(3):
+    assert len(runs[0]) == len(runs[1]) > 0
+    for s in range(len(runs[0])):
         a, b = runs[0][s], runs[1][s]
         late = s >= 2
         checks = [("Lio", 1e-9, 1e-12 * np.abs(a["Lio"]).max()), ("hio", 1e-9, 1e-12 * max(np.abs(a["hio"]).max(), 1.0)),
@@ -149,4 +140,13 @@ def test_scans_with_device_branch_match_host_branch(mode, B, cap, n):
         rt[49 - 42] = 1e-4
         if not np.all(np.abs(cb - ca) <= rt * np.abs(ca) + 1e-12):
             bad.append((s, "cert[42:57]", [float(x) for x in (np.abs(cb - ca) / (np.abs(ca) + 1e-12))]))
+    return bad
+
+
+@pytest.mark.parametrize("mode,B,cap,n", [("dense", 48, 2048, 4096), ("scale", 20000, 8192, 8192)])
+def test_scans_with_device_branch_match_host_branch(mode, B, cap, n):
+    """Three consecutive 14-step scans with the device IMU / odometry branch against the same scans with
+    the host branch: z_t, the belief, the IMU / odometry evidence and its certificates."""
+    runs = _scans_both_branches([synthetic.make_scan(n, 120 + s) for s in range(3)], mode, B, cap, n)
+    bad = _branch_mismatches(runs)
     assert not bad, bad

@@ -80,32 +80,44 @@ def test_k_preint_matches_oracle(kind, rotation_only):
         assert np.all(out[:6] == 0.0) and np.all(out[7:16] == 0.0)
 
 
-def test_scan_device_preint_matches_host_prologue():
-    """gcs_scan with GCS_DEBUG_DEVICE_PREINT = 1 (k_preint on the stream ahead of k_points, the twist
-    through the device word) against the host prologue, three consecutive scans: the posterior, the
-    scan statistics and the map agree at the full-pipeline bars, and the ess certificate (cert[10])
-    to 1e-13."""
+def _scans_both_prologues(scans, **ctx_kw):
+    """The scans through one context per prologue (k_preint's, then the host's): per scan the statistics,
+    the map, the belief's L, z_t and the certificates."""
     from gcslam import _lib as L
-    from gcslam import synthetic as syn
     from gcslam.context import HypothesisContext
     outs = []
     for dev in (1, 0):
-        ctx = HypothesisContext(lidar_origin=(0.0, 0.0, 0.5), max_raw_points=1 << 20, n_bins=20000,
-                                n_points_cap=8192, mode="scale")
-        ctx.set_debug(L.DEBUG_DEVICE_PREINT, dev)
+        ctx = HypothesisContext(lidar_origin=(0.0, 0.0, 0.5), **ctx_kw)
         res = []
-        for k in range(3):
-            sc = syn.make_scan(8192, 51 + k)
-            rec, t, w = device_scan(sc)
-            o = ctx.scan(rec, 16, t, w, 8192, **scan_kwargs(sc))
-            res.append((ctx.get_scan_stats(), ctx.get_map()[0], np.array(o.belief.L[:]), np.array(o.z_t[:]),
-                        np.array(o.cert[:])))
+        try:
+            ctx.set_debug(L.DEBUG_DEVICE_PREINT, dev)
+            for sc in scans:
+                rec, t, w = device_scan(sc)
+                o = ctx.scan(rec, 16, t, w, rec.shape[0], **scan_kwargs(sc))
+                res.append((ctx.get_scan_stats(), ctx.get_map()[0], np.array(o.belief.L[:]), np.array(o.z_t[:]),
+                            np.array(o.cert[:])))
+        finally:
+            ctx.close()
         outs.append(res)
-        ctx.close()
-    for k in range(3):
-        (sa, ma, La, za, ca), (sb, mb, Lb, zb, cb) = outs[0][k], outs[1][k]
+    return outs
+
+
+def _assert_prologues_agree(outs):
+    assert len(outs[0]) == len(outs[1]) > 0
+    for (sa, ma, La, za, ca), (sb, mb, Lb, zb, cb) in zip(*outs):
         assert ca[10] == pytest.approx(cb[10], rel=1e-13)
         np.testing.assert_allclose(za, zb, rtol=1e-7, atol=1e-9)
         np.testing.assert_allclose(La, Lb, rtol=1e-7, atol=1e-7 * np.abs(Lb).max())
         np.testing.assert_allclose(sa, sb, rtol=1e-7, atol=1e-9 * max(np.abs(sb).max(), 1.0))
         np.testing.assert_allclose(ma, mb, rtol=1e-7, atol=1e-9 * max(np.abs(mb).max(), 1.0))
+
+
+def test_scan_device_preint_matches_host_prologue():
+    """gcs_scan with GCS_DEBUG_DEVICE_PREINT = 1 (k_preint on the stream ahead of k_points, the twist
+    through the device word) against the host prologue, three consecutive scans: the posterior, the
+    scan statistics and the map agree at the full-pipeline bars, and the ess certificate (cert[10])
+    to 1e-13."""
+    from gcslam import synthetic as syn
+    outs = _scans_both_prologues([syn.make_scan(8192, 51 + k) for k in range(3)], max_raw_points=1 << 20,
+                                 n_bins=20000, n_points_cap=8192, mode="scale")
+    _assert_prologues_agree(outs)

@@ -57,9 +57,9 @@ def _hip(lib, d):
     return Lm.reshape(22, 22), h, cert
 
 
-def _check(lib, d):
-    L_o, h_o, named, info, dt_int, dt_imu, om = _oracle(d)
-    L_h, h_h, cert = _hip(lib, d)
+def _compare(L_h, h_h, cert, oracle):
+    """One branch's evidence and certificates (the host's or the device's) against _oracle's tuple."""
+    L_o, h_o, named, info, dt_int, dt_imu, om = oracle
     sc = np.abs(L_o).max()
     np.testing.assert_allclose(L_h, L_o, rtol=1e-9, atol=1e-12 * sc)
     np.testing.assert_allclose(h_h, h_o, rtol=1e-9, atol=1e-12 * max(np.abs(h_o).max(), 1.0))
@@ -70,6 +70,12 @@ def _check(lib, d):
                                             named["gyro"]["nll_per_ess"]], rtol=1e-8, atol=1e-12)
     np.testing.assert_allclose(cert[10:15], [dt_int, dt_imu, *om], **TOL)
     assert np.all(np.isfinite(L_h)) and np.allclose(L_h, L_h.T, atol=1e-9 * sc)
+
+
+def _check(lib, d):
+    oracle = _oracle(d)
+    _compare(*_hip(lib, d), oracle)
+    L_o, h_o, named, info = oracle[:4]
     return L_o, h_o, info
 
 
