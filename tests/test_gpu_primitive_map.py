@@ -8,38 +8,12 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from oracle import primitive_map as opm
+from pmap_shape_util import rand_tile as _rand_tile
 
 pytestmark = pytest.mark.gpu
 
 M = 4096
 NL = 3
-
-
-def _rand_tile(rng, m=M, frac=0.6, seq_hi=40):
-    t = opm.create_empty_tile(m)
-    v = rng.random(m) < frac
-    t["valid_mask"][:] = v
-    w = rng.random(m) * 2.0
-    w[rng.random(m) < 0.1] = 0.5          # exact ties (stable order by slot)
-    w[rng.random(m) < 0.05] = 0.0
-    t["weights"][:] = w
-    A = rng.normal(size=(m, 3, 3)) * 0.3
-    t["Lambdas"][:] = np.einsum("nij,nkj->nik", A, A) + np.eye(3)[None] * rng.uniform(0.5, 4.0, size=(m, 1, 1))
-    t["thetas"][:] = rng.normal(size=(m, 3)) * 3.0
-    t["etas"][:] = rng.normal(size=(m, NL, 3))
-    t["timestamps"][:] = rng.uniform(0, 10, m)
-    t["created_timestamps"][:] = rng.uniform(0, 10, m)
-    t["last_supported_scan_seq"][:] = rng.integers(0, seq_hi, m)
-    t["last_update_scan_seq"][:] = rng.integers(0, seq_hi, m)
-    t["primitive_ids"][:] = rng.permutation(10 * m)[:m]
-    t["colors"][:] = rng.random((m, 3))
-    cam = np.where(rng.random(m) < 0.3, rng.random(m), 0.0)
-    t["cam_mass"][:] = cam
-    t["lidar_mass"][:] = rng.random(m)
-    t["rgb_cam_accum"][:] = rng.random((m, 3)) * cam[:, None]
-    t["rgb_cam_denom"][:] = cam
-    t["rgb"][:] = np.where((cam > 0)[:, None], rng.random((m, 3)), 0.5)
-    return t
 
 
 def _map(tiles, m=M, max_merge=0):
