@@ -199,6 +199,20 @@ class GcsVisfeatOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n, _, _ in VISFEAT_FEATURE_FIELDS + VISFEAT_DIAG_FIELDS] + [("count", C.c_int32)]
 
 
+class GcsKeypointConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("fast_threshold", "edge_threshold", "max_keypoints", "max_width",
+                                         "max_height")] + [("harris_k", C.c_double), ("device", C.c_int32)]
+
+
+class GcsKeypointInputs(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("channels", C.c_int32), ("pitch", C.c_int64), ("width", C.c_int32),
+                ("height", C.c_int32)]
+
+
+class GcsKeypointOutputs(C.Structure):
+    _fields_ = [("kp_u", C.c_void_p), ("kp_v", C.c_void_p), ("kp_response", C.c_void_p), ("counts", C.c_void_p)]
+
+
 class GcsRenderConfig(C.Structure):
     _fields_ = [("tile_size", C.c_int32), ("max_splats_per_tile", C.c_int32), ("fbm_octaves", C.c_int32),
                 ("fbm_gain", C.c_double), ("opacity_gamma", C.c_double), ("logdet0", C.c_double), ("eps", C.c_double),
@@ -459,6 +473,14 @@ _SIGS = [
     ("gcs_visual_features", C.c_int, [C.c_void_p, C.POINTER(GcsVisfeatInputs), C.POINTER(GcsVisfeatOutputs)]),
     ("gcs_visual_features_host", C.c_int, [C.POINTER(GcsVisfeatConfig), C.POINTER(GcsVisfeatInputs),
                                            C.POINTER(GcsVisfeatOutputs)]),
+    ("gcs_keypoint_config_defaults", C.c_int, [C.POINTER(GcsKeypointConfig)]),
+    ("gcs_keypoint_ctx_create", C.c_int, [C.POINTER(GcsKeypointConfig), C.POINTER(C.c_void_p)]),
+    ("gcs_keypoint_ctx_destroy", C.c_int, [C.c_void_p]),
+    ("gcs_keypoint_last_error", C.c_char_p, [C.c_void_p]),
+    ("gcs_keypoint_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gcs_detect_keypoints", C.c_int, [C.c_void_p, C.POINTER(GcsKeypointInputs), C.POINTER(GcsKeypointOutputs)]),
+    ("gcs_detect_keypoints_host", C.c_int, [C.POINTER(GcsKeypointConfig), C.POINTER(GcsKeypointInputs),
+                                            C.POINTER(GcsKeypointOutputs)]),
     ("gcs_render_config_defaults", C.c_int, [C.POINTER(GcsRenderConfig)]),
     ("gcs_render_ctx_create", C.c_int, [C.POINTER(GcsRenderConfig), C.POINTER(C.c_void_p)]),
     ("gcs_render_ctx_destroy", C.c_int, [C.c_void_p]),

@@ -5,8 +5,10 @@ closed-form covariance, the medial-axis inflation, the vMF kappa, weights and co
 _feature_batch_to_list (FS/backend/backend_node.py:1589-1650) makes of the message rows, through
 gcs_visual_features (libgcslam_hip.so).  The result is the device feature dict of gcslam.camera: it goes
 to CameraSplatBuilder.build or, in a CameraFrame, to process_scan_single_hypothesis, with no host copy.
-The keypoint detector is the caller's: keypoints are (u, v, response) rows, cv::KeyPoint's pt.x, pt.y and
-response."""
+Keypoints are (u, v, response) rows, cv::KeyPoint's pt.x, pt.y and response: the caller's, from any
+detector, or with keypoints=None the library's own (gcslam.keypoints: FAST-9, Harris response, stable top-N
+at pyramid level 0, no parity with cv::ORB), detected from rgb on the same stream and passed device to
+device."""
 
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ import numpy as np
 
 from . import _lib as L
 from .camera import CameraFrame, DepthFusionConfig, PinholeIntrinsics, _DeviceFeatures
+from .keypoints import KeypointConfig, detect_keypoints
 
 _MODES = {"nearest": L.VF_NEAREST, "median3": L.VF_MEDIAN3, "median5": L.VF_MEDIAN5, "hex": L.VF_HEX}
 _MODELS = {"linear": L.VF_DEPTH_LINEAR, "quadratic": L.VF_DEPTH_QUADRATIC}
@@ -167,13 +170,17 @@ class VisualFeatureExtractor:
         return x
 
     def extract(self, depth, rgb, keypoints, intrinsics: PinholeIntrinsics, want_diag: bool = False,
-                trim: bool = True) -> _DeviceFeatures:
+                trim: bool = True, keypoint_config: Optional[KeypointConfig] = None) -> _DeviceFeatures:
         """One frame's features as gcslam.camera's device feature dict, on the current torch stream and
         without waiting for it.  depth: (H, W) float32 or uint16 (metres = value * depth_scale), rgb:
         (H, W, 3) uint8 or None; torch device tensors, or numpy arrays (uploaded once).  keypoints: (n, 3)
         u, v, response or three arrays.  The dict's arrays hold .count = min(n, max_features) rows (trim
-        False: all max_features, zeros beyond count); .diag (want_diag) the per-feature diagnostics."""
+        False: all max_features, zeros beyond count); .diag (want_diag) the per-feature diagnostics.
+        keypoints None: detected from rgb (gcslam.keypoints.detect_keypoints with keypoint_config) on the same
+        stream; that route waits once, for the detector's 16-byte counts word."""
         import torch
+        if keypoints is None and rgb is None:
+            raise ValueError("keypoints=None needs rgb: the keypoints are detected from it")
         dev = torch.device(f"cuda:{self.device}")
         d = self._image(depth, (np.float32, np.uint16))
         if d.ndim != 2:
@@ -184,6 +191,8 @@ class VisualFeatureExtractor:
             c = self._image(rgb, (np.uint8,))
             if tuple(c.shape) != (H, W, 3):
                 raise ValueError(f"rgb: shape {tuple(c.shape)}, expected {(H, W, 3)}")
+        if keypoints is None:
+            keypoints = detect_keypoints(c, keypoint_config, self.device)
         kp = [torch.as_tensor(np.asarray(k, np.float32) if not torch.is_tensor(k) else k).to(dev, torch.float32)
               .contiguous() for k in _keypoint_arrays(keypoints)]
         n = int(kp[0].shape[0])
@@ -222,10 +231,11 @@ def _extractor_for(config, device) -> VisualFeatureExtractor:
 
 def extract_visual_features(depth, rgb, keypoints, intrinsics: PinholeIntrinsics,
                             config: Optional[VisualFeatureConfig] = None, device: int = 0, want_diag: bool = False,
-                            trim: bool = True) -> _DeviceFeatures:
+                            trim: bool = True, keypoint_config: Optional[KeypointConfig] = None) -> _DeviceFeatures:
     """VisualFeatureExtractor.extract on a cached extractor of (config, device)."""
     return _extractor_for(config or VisualFeatureConfig(), device).extract(depth, rgb, keypoints, intrinsics,
-                                                                           want_diag=want_diag, trim=trim)
+                                                                           want_diag=want_diag, trim=trim,
+                                                                           keypoint_config=keypoint_config)
 
 
 def visual_features_host(depth, rgb, keypoints, intrinsics: PinholeIntrinsics,
@@ -271,10 +281,14 @@ def visual_features_host(depth, rgb, keypoints, intrinsics: PinholeIntrinsics,
 def camera_frame_from_rgbd(depth, rgb, keypoints, intrinsics: PinholeIntrinsics, R_base_camera, t_base_camera,
                            timestamp_sec: float, config: Optional[VisualFeatureConfig] = None,
                            fusion_config: Optional[DepthFusionConfig] = None, device: int = 0,
-                           want_diag: bool = False, max_candidates: int = 1024) -> CameraFrame:
+                           want_diag: bool = False, max_candidates: int = 1024,
+                           keypoint_config: Optional[KeypointConfig] = None) -> CameraFrame:
     """on_rgbd after detectAndCompute, the VisualFeatureBatch and _feature_batch_to_list in one step: the
     frame's features extracted on the GPU and held there in a CameraFrame for
-    process_scan_single_hypothesis(camera_batch=..., camera_batch_policy="use")."""
-    feats = extract_visual_features(depth, rgb, keypoints, intrinsics, config=config, device=device)
+    process_scan_single_hypothesis(camera_batch=..., camera_batch_policy="use").  keypoints None: detectAndCompute's
+    detector front as well, from rgb (gcslam.keypoints), so a node without a detector of its own passes the
+    two images and nothing else."""
+    feats = extract_visual_features(depth, rgb, keypoints, intrinsics, config=config, device=device,
+                                    keypoint_config=keypoint_config)
     return CameraFrame(feats, intrinsics, R_base_camera, t_base_camera, timestamp_sec,
                        config=fusion_config or DepthFusionConfig(), want_diag=want_diag, max_candidates=max_candidates)

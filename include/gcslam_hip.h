@@ -699,8 +699,10 @@ int gcs_camera_splats_scan(gcs_camsplat_ctx* ctx, const gcs_camsplat_inputs* in,
  * colour (:546-641), and _feature_batch_to_list's renormalised mu_app (backend_node.py:1589-1650).
  * One wave64 per keypoint, one lane per window pixel, all f64; the median is an input value picked
  * by rank (element n / 2 of the sorted valid values, ties by lane) and the normal equations are
- * butterfly sums in a fixed order, so two calls agree bit for bit.  The keypoint detector (ORB) is not
- * part of the library: kp_u, kp_v, kp_response are cv::KeyPoint's pt.x, pt.y, response.
+ * butterfly sums in a fixed order, so two calls agree bit for bit.  kp_u, kp_v, kp_response are
+ * cv::KeyPoint's pt.x, pt.y, response: from any detector of the caller's, or from gcs_detect_keypoints
+ * below, the library's own FAST-9 / Harris detector at pyramid level 0 (ORB's pyramid, orientation and
+ * descriptors are not part of the library, and its detector claims no parity with cv::ORB).
  * Declared where the node leaves it open: with n_keypoints > max_features the max_features largest
  * responses are kept (ties to the lower index, NaN last) and written in input order; a keypoint with
  * a non-finite u or v, or |u| or |v| > 1e9, is outside the image; a NaN response weighs 0.  A keypoint
@@ -787,6 +789,74 @@ int gcs_visual_features(gcs_visfeat_ctx* ctx, const gcs_visfeat_inputs* in, gcs_
 /* The same rows on the host (no device, no context): every pointer is a host array. */
 int gcs_visual_features_host(const gcs_visfeat_config* cfg, const gcs_visfeat_inputs* in,
                              gcs_visfeat_outputs* out);
+
+/* ---------------------------------------------------------------- primitive path: keypoint detector */
+/* Keypoints from an 8-bit image on the GPU, in the form gcs_visfeat_inputs reads.  This detector is the
+ * project's own.  It follows the published FAST / ORB recipe, but it claims no parity with cv::ORB: there
+ * is no pyramid (ORB's nlevels = 8, scaleFactor = 1.2), there is no orientation, and there are no
+ * descriptors.  Everything is exact integer arithmetic except the last step of the response:
+ *  1. grey: gray8 as it is; rgb8 as g = (4899 R + 9617 G + 1868 B + 8192) >> 14.
+ *  2. FAST-9/16 score: the ring is the radius-3 Bresenham circle, clockwise from the top: (0,-3) (1,-3)
+ *     (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3).
+ *     With d_j = I(ring_j) - I(p), m(p) = max over the 16 arcs of 9 consecutive ring positions of
+ *     max(min_arc d_j, min_arc -d_j); p (3 <= x < W - 3, 3 <= y < H - 3) is a corner when
+ *     m(p) > fast_threshold and its score is then m(p); every other pixel's score is 0.
+ *  3. suppression: a corner survives when its score is strictly greater than its 8 neighbours' scores
+ *     (two adjacent corners of equal score both go); neighbours outside the border of 4. compete.
+ *  4. border: survivors with edge_threshold <= x < W - edge_threshold, and the same in y, are kept; an
+ *     image too small to hold one such pixel yields zero keypoints and is not an error.
+ *  5. response: over the 7 x 7 block around the survivor, with Ix, Iy the 3 x 3 Sobel derivatives of the
+ *     grey image as integers, a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy (int64);
+ *     r = ((double)(a b - c c) - harris_k (double)((a + b)(a + b))) s^4, s = 1.0 / (4 * 7 * 255), every
+ *     operation rounded on its own, s^4 formed as ((s s) s) s, the result rounded once to float32
+ *     (ORB's Harris score with its scale: about 1e-4 .. 1e-2).
+ *  6. selection: with more than max_keypoints survivors exactly the max_keypoints largest by (response
+ *     descending, raster index y W + x ascending) are kept.  Output is always in raster order, kp_u = x,
+ *     kp_v = y; rows [n_keypoints, max_keypoints) of the three arrays are NaN, which
+ *     gcs_visual_features ranks last, weighs 0 and treats as outside the image, so a caller may chain
+ *     with n_keypoints = max_keypoints and no wait.
+ * No intermediate capacity exists that an image could overflow: the only buffers sized by the image are
+ * per-pixel, and the selection is a radix select over the per-pixel key image.  No kernel reads outside
+ * [0, W) x [0, H) of the input.  Calls on one context must be serialised. */
+typedef struct gcs_keypoint_ctx gcs_keypoint_ctx;
+
+typedef struct {
+  int32_t fast_threshold;        /* 20 (ORB's fastThreshold); 0 .. 255 */
+  int32_t edge_threshold;        /* 31 (ORB's edgeThreshold); >= 4 */
+  int32_t max_keypoints;         /* 4096; 1 .. 65536 (gcs_visfeat_config.max_keypoints' range) */
+  int32_t max_width, max_height; /* 1920 x 1080: capacity of the per-pixel workspace (at most 2^28 pixels) */
+  double harris_k;               /* 0.04; finite */
+  int32_t device;
+} gcs_keypoint_config;
+
+/* One image.  Device pointers for gcs_detect_keypoints, host pointers for gcs_detect_keypoints_host. */
+typedef struct {
+  const uint8_t* image;          /* height rows, pitch bytes apart */
+  int32_t channels;              /* 1: gray8, 3: rgb8 */
+  int64_t pitch;                 /* >= channels * width */
+  int32_t width, height;         /* >= 1, at most the context's max_width, max_height */
+} gcs_keypoint_inputs;
+
+typedef struct {
+  float *kp_u, *kp_v, *kp_response;   /* max_keypoints each */
+  int32_t* counts;               /* 4: n_keypoints, n_survivors (after the border, before the cap), n_corners
+                                    (pixels with a non-zero score), 0 */
+} gcs_keypoint_outputs;
+
+int gcs_keypoint_config_defaults(gcs_keypoint_config* cfg);
+/* GCS_ERR_ARG, before any device call, for a config outside the ranges above. */
+int gcs_keypoint_ctx_create(const gcs_keypoint_config* cfg, gcs_keypoint_ctx** out);
+int gcs_keypoint_ctx_destroy(gcs_keypoint_ctx* ctx);
+const char* gcs_keypoint_last_error(const gcs_keypoint_ctx* ctx);
+/* stream: as gcs_visfeat_ctx_set_stream -- the context queues on the caller's stream and waits for nothing */
+int gcs_keypoint_ctx_set_stream(gcs_keypoint_ctx* ctx, void* stream);
+/* Queues its kernels on the context's stream and returns; counts is a device array like the others.
+ * GCS_ERR_ARG, before any device call, for channels not 1 or 3, width or height < 1 or above the
+ * context's capacity, pitch < channels * width, or a null array. */
+int gcs_detect_keypoints(gcs_keypoint_ctx* ctx, const gcs_keypoint_inputs* in, gcs_keypoint_outputs* out);
+/* The same steps on the host (no device, no context): every pointer is a host array. */
+int gcs_detect_keypoints_host(const gcs_keypoint_config* cfg, const gcs_keypoint_inputs* in,
+                              gcs_keypoint_outputs* out);
 
 /* ---------------------------------------------------------------- primitive path: map rendering */
 /* The reference's output side (backend/rendering.py, common/bev_pushforward.py) on the GPU, reading

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Timing of the keypoint detector at the node's frame size: a 640 x 480 rgb8 frame on the device (noisy blocks
+of 16 px, the `vga` fixture of tests/keypoints_ref.py restated here), the default KeypointConfig, and a
+640 x 480 float32 depth image for the feature operator behind it.  Timed in one process with stream events,
+each route after its own warm-up, the median of REPEAT calls:
+
+  detect            gcslam.keypoints.KeypointDetector.detect: the kernels and the 16-byte counts read-back
+  queue             the kernels alone (KeypointDetector.queue: nothing is waited for inside the timed call)
+  readback          the 16-byte pinned read-back and its wait alone, on an idle stream
+  extract_detect    VisualFeatureExtractor.extract(depth, rgb, None, K): detector and feature operator chained
+  extract_upload    the same keypoints passed as pageable numpy arrays: the only route before the detector
+  extract_device    the same keypoints already on the device (the feature operator alone)
+
+--profile runs `detect` only, WARMUP + REPEAT times, for a kernel trace taken from outside.  Prints one JSON
+line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "gc-slam_amd"), ROOT]
+
+W, H, WARMUP, REPEAT = 640, 480, 20, 200
+
+
+def frame(np):
+    g = np.random.default_rng(20)
+    colours = g.integers(0, 256, (H // 16, W // 16, 3))
+    img = np.repeat(np.repeat(colours, 16, 0), 16, 1) + g.integers(-6, 7, (H, W, 3))
+    rgb = np.clip(img, 0, 255).astype(np.uint8)
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    depth = (3.0 + 0.002 * (x - 320.0) + 1e-5 * (y - 240.0) ** 2 + 0.01 * g.standard_normal((H, W))).astype(np.float32)
+    return rgb, depth
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--profile", action="store_true")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    from gcslam import keypoints as KP
+    from gcslam import visual as V
+    from gcslam.camera import PinholeIntrinsics
+
+    rgb, depth = frame(np)
+    rgb_d, depth_d = torch.from_numpy(rgb).cuda(), torch.from_numpy(depth).cuda()
+    K = PinholeIntrinsics(500.0, 500.0, 320.0, 240.0)
+    det = KP.KeypointDetector()
+    ex = V.VisualFeatureExtractor(V.VisualFeatureConfig(response_soft_scale=1e-3))
+    kp = det.detect(rgb_d)
+    kp_host = tuple(k.cpu().numpy() for k in kp)
+
+    def timed(fn):
+        ms = []
+        for i in range(WARMUP + REPEAT):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= WARMUP:
+                ms.append(a.elapsed_time(b))
+        ms.sort()
+        return statistics.median(ms), (ms[len(ms) // 10], ms[-1 - len(ms) // 10])   # median, 10th .. 90th percentile
+
+    if args.profile:
+        for _ in range(WARMUP + REPEAT):
+            det.detect(rgb_d)
+        print(json.dumps(dict(profile_calls=WARMUP + REPEAT)))
+        return
+
+    pinned = torch.empty(4, dtype=torch.int32).pin_memory()
+    counts_d = torch.zeros(4, dtype=torch.int32, device="cuda")
+
+    def readback():
+        pinned.copy_(counts_d, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        ev.synchronize()
+
+    out = dict(width=W, height=H, warmup=WARMUP, repeat=REPEAT, counts=list(kp.counts))
+    for name, fn in (("detect", lambda: det.detect(rgb_d)),
+                     ("queue", lambda: det.queue(rgb_d)),
+                     ("readback", readback),
+                     ("extract_detect", lambda: ex.extract(depth_d, rgb_d, None, K)),
+                     ("extract_upload", lambda: ex.extract(depth_d, rgb_d, kp_host, K)),
+                     ("extract_device", lambda: ex.extract(depth_d, rgb_d, kp, K))):
+        out[name + "_ms"], out[name + "_ms_p10_p90"] = timed(fn)
+    print(json.dumps(out))
+    det.close()
+    ex.close()
+
+
+if __name__ == "__main__":
+    main()
