@@ -18,6 +18,17 @@
 // Histograms are per workgroup in LDS and merged with integer atomics, so every run gives the same bytes.
 // Each select kernel redoes the 256-bin suffix scan of the byte before it, so no launch exists only to
 // pick a bin.  The math is gcs_keypoints_math.h, which gcs_detect_keypoints_host runs on the host.
+//
+// gcs_detect_keypoints_pyramid runs the same detector over a scale pyramid (the definition: P1-P5 in
+// include/gcslam_hip.h) in one memset and nine launches whatever n_levels is: the levels' grey, score and key
+// images are packed one after another (KpLevels), the bodies of the kernels above are __device__ functions of a
+// tile or a strip, and the k_kpp_* kernels look their level up from blockIdx.x:
+//   k_kpp_resample every level's grey image from the input (level 0: the grey conversion; level l: the exact
+//                  pixel-area mean over its footprint, in integers)
+//   k_kpp_score, k_kpp_response, k_kpp_hist x 3, k_kpp_count   the tile / strip functions on the block's level,
+//                  with per-level histograms, select state and quota
+//   k_kpp_scan     one workgroup over all levels' strips; per-level and total counts, each level's first row
+//   k_kpp_emit     level-major, raster-within-level rows in level-0 coordinates, with kp_level
 
 #include <hip/hip_runtime.h>
 
@@ -64,14 +75,18 @@ struct KpWork {
 
 // ---- k_kp_score
 
-template <int CH>
-__global__ __launch_bounds__(kKpThreads) void k_kp_score(const uint8_t* __restrict__ img, int64_t pitch, int W, int H,
-                                                         int threshold, uint8_t* __restrict__ grey_out,
-                                                         uint8_t* __restrict__ score_out, uint32_t* __restrict__ n_corners) {
+// The tile at (x0, y0) of a W x H image, by one workgroup; a kernel calls it once.  GREY_OUT false: img is the
+// grey image itself (CH 1) and is not written again.  The LDS arrays of this and the other per-tile and
+// per-strip functions are declared inside them, not handed in by pointer: through a generic pointer the compiler
+// folded k_kp_response's list store and its key store into one flat store, and list entries written that way
+// were not all seen behind the barrier on gfx950 (counts changed from run to run).
+template <int CH, bool GREY_OUT>
+__device__ __forceinline__ void kp_score_tile(const uint8_t* __restrict__ img, int64_t pitch, int W, int H, int threshold,
+                                              uint8_t* __restrict__ grey_out, uint8_t* __restrict__ score_out,
+                                              uint32_t* __restrict__ n_corners, int x0, int y0) {
   __shared__ uint32_t raw[kKpGH * kKpRawDw];
   __shared__ uint8_t grey[kKpGH * kKpGStride];
   const int t = threadIdx.x;
-  const int x0 = blockIdx.x * kKpTileW, y0 = blockIdx.y * kKpTileH;
   const int xa = max(x0 - kKpFrame, 0), xb = min(x0 + kKpTileW + kKpFrame, W);   // the tile's columns inside the image
   for (int idx = t; idx < kKpGH * kKpRawDw; idx += kKpThreads) {
     const int r = idx / kKpRawDw, i = idx % kKpRawDw;
@@ -112,7 +127,7 @@ __global__ __launch_bounds__(kKpThreads) void k_kp_score(const uint8_t* __restri
       const uint8_t* c = &grey[(ly + kKpFrame) * kKpGStride + lx + kKpFrame];
       int s = 0;
       if (x >= kKpFrame && x < W - kKpFrame && y >= kKpFrame && y < H - kKpFrame) s = kp_fast_score(c, kKpGStride, threshold);
-      grey_out[y * W + x] = c[0];
+      if (GREY_OUT) grey_out[y * W + x] = c[0];
       score_out[y * W + x] = (uint8_t)s;
       corners += s > 0;
     }
@@ -121,17 +136,25 @@ __global__ __launch_bounds__(kKpThreads) void k_kp_score(const uint8_t* __restri
   if ((t & 63) == 0 && corners) atomicAdd(n_corners, (uint32_t)corners);
 }
 
+template <int CH>
+__global__ __launch_bounds__(kKpThreads) void k_kp_score(const uint8_t* __restrict__ img, int64_t pitch, int W, int H,
+                                                         int threshold, uint8_t* __restrict__ grey_out,
+                                                         uint8_t* __restrict__ score_out, uint32_t* __restrict__ n_corners) {
+  kp_score_tile<CH, true>(img, pitch, W, H, threshold, grey_out, score_out, n_corners, blockIdx.x * kKpTileW,
+                          blockIdx.y * kKpTileH);
+}
+
 // ---- k_kp_response
 
-__global__ __launch_bounds__(kKpThreads) void k_kp_response(const uint8_t* __restrict__ score, const uint8_t* __restrict__ grey,
-                                                            int W, int H, int edge, double harris_k,
-                                                            uint32_t* __restrict__ key, uint32_t* __restrict__ ghist) {
+// the tile at (x0, y0) of a W x H image; ghist: the 256 bins of the keys' top byte
+__device__ __forceinline__ void kp_response_tile(const uint8_t* __restrict__ score, const uint8_t* __restrict__ grey, int W,
+                                                 int H, int edge, double harris_k, uint32_t* __restrict__ key,
+                                                 uint32_t* __restrict__ ghist, int x0, int y0) {
   __shared__ uint8_t sc[kKpSH * kKpSStride];
   __shared__ int list[kKpTileW * kKpTileH];
   __shared__ int n_list;
   __shared__ uint32_t hist[kKpBins];
   const int t = threadIdx.x;
-  const int x0 = blockIdx.x * kKpTileW, y0 = blockIdx.y * kKpTileH;
   for (int idx = t; idx < kKpSH * kKpSW; idx += kKpThreads) {
     const int r = idx / kKpSW, c = idx % kKpSW;
     const int x = x0 - 1 + c, y = y0 - 1 + r;
@@ -180,6 +203,12 @@ __global__ __launch_bounds__(kKpThreads) void k_kp_response(const uint8_t* __res
   if (hist[t]) atomicAdd(&ghist[t], hist[t]);
 }
 
+__global__ __launch_bounds__(kKpThreads) void k_kp_response(const uint8_t* __restrict__ score, const uint8_t* __restrict__ grey,
+                                                            int W, int H, int edge, double harris_k,
+                                                            uint32_t* __restrict__ key, uint32_t* __restrict__ ghist) {
+  kp_response_tile(score, grey, W, H, edge, harris_k, key, ghist, blockIdx.x * kKpTileW, blockIdx.y * kKpTileH);
+}
+
 // ---- the select
 
 // Byte q of the select from its histogram (counts of that byte over the keys sharing prev.prefix's higher
@@ -212,9 +241,9 @@ __device__ KpSel kp_resolve(const uint32_t* __restrict__ hist_q, KpSel prev, int
   return cur;
 }
 
-// a thread's keys of its strip: [blockIdx.x * 2048 + 8 t, + 8), zeros beyond n (the allocation is whole strips)
-__device__ inline int kp_load_keys(const uint32_t* __restrict__ key, int n, uint32_t* k) {
-  const int i0 = blockIdx.x * kKpStrip + threadIdx.x * kKpPerThread;
+// a thread's keys of strip `strip`: [strip * 2048 + 8 t, + 8), zeros beyond n (the allocation is whole strips)
+__device__ inline int kp_load_keys(const uint32_t* __restrict__ key, int strip, int n, uint32_t* k) {
+  const int i0 = strip * kKpStrip + threadIdx.x * kKpPerThread;
   const uint4 lo = *(const uint4*)(key + i0), hi = *(const uint4*)(key + i0 + 4);
   const uint32_t v[kKpPerThread] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
@@ -222,25 +251,31 @@ __device__ inline int kp_load_keys(const uint32_t* __restrict__ key, int n, uint
   return i0;
 }
 
-__global__ __launch_bounds__(kKpThreads) void k_kp_hist(const uint32_t* __restrict__ key, int n, int K, int pass,
-                                                        uint32_t* __restrict__ ghist, KpSel* __restrict__ st) {
+// One strip of a key image of n keys in pass `pass` of the select of the K largest; ghist: 4 x 256 bins, st: [1..4].
+__device__ __forceinline__ void kp_hist_strip(const uint32_t* __restrict__ key, int strip, int n, int K, int pass,
+                                              uint32_t* __restrict__ ghist, KpSel* __restrict__ st) {
   __shared__ uint32_t s[kKpBins];
   __shared__ KpSel box;
   const int t = threadIdx.x;
   const KpSel first = {0u, K, 0, 0};
   const KpSel cur = kp_resolve(ghist + (pass - 1) * kKpBins, pass == 1 ? first : st[pass - 1], pass - 1, s, &box);
-  if (blockIdx.x == 0 && t == 0) st[pass] = cur;
+  if (strip == 0 && t == 0) st[pass] = cur;
   if (cur.all) return;
   s[t] = 0;
   __syncthreads();
   uint32_t k[kKpPerThread];
-  kp_load_keys(key, n, k);
+  kp_load_keys(key, strip, n, k);
   const int shift = 32 - 8 * pass;
 #pragma unroll
   for (int j = 0; j < kKpPerThread; ++j)   // (a key of 0 shares no chosen byte: the top byte of a real key is never 0)
     if (k[j] && (k[j] >> shift) == (cur.prefix >> shift)) atomicAdd(&s[(k[j] >> (shift - 8)) & 255u], 1u);
   __syncthreads();
   if (s[t]) atomicAdd(&ghist[pass * kKpBins + t], s[t]);
+}
+
+__global__ __launch_bounds__(kKpThreads) void k_kp_hist(const uint32_t* __restrict__ key, int n, int K, int pass,
+                                                        uint32_t* __restrict__ ghist, KpSel* __restrict__ st) {
+  kp_hist_strip(key, blockIdx.x, n, K, pass, ghist, st);
 }
 
 __device__ inline int kp_wave_incl(int x) {
@@ -252,17 +287,30 @@ __device__ inline int kp_wave_incl(int x) {
   return x;
 }
 
-__global__ __launch_bounds__(kKpThreads) void k_kp_count(const uint32_t* __restrict__ key, int n, const uint32_t* __restrict__ ghist,
-                                                         KpSel* __restrict__ st, int2* __restrict__ strip_cnt) {
+// The cut of a finished select: keys above kth are kept, and of the keys equal to it the first `need` in raster
+// order.  A quota of 0 (a pyramid level's; the select then ran for rank 1) keeps nothing: no finite
+// response has the key 0xffffffff.
+__device__ inline void kp_cut(const KpSel cur, int quota, uint32_t* kth, int* need) {
+  *kth = quota == 0 ? 0xffffffffu : cur.all ? 0u : cur.prefix;
+  *need = (quota == 0 || cur.all) ? 0 : cur.rem;
+}
+__device__ inline int kp_kept(const KpSel cur, int quota) { return quota == 0 ? 0 : cur.all ? cur.total : quota; }
+
+// resolves the last byte and counts one strip; cnt: the strip's (above kth, equal to kth)
+__device__ __forceinline__ void kp_count_strip(const uint32_t* __restrict__ key, int strip, int n, int quota,
+                                               const uint32_t* __restrict__ ghist, KpSel* __restrict__ st,
+                                               int2* __restrict__ cnt) {
   __shared__ uint32_t s[kKpBins];
   __shared__ KpSel box;
   __shared__ int2 part[kKpThreads / 64];
   const int t = threadIdx.x;
   const KpSel cur = kp_resolve(ghist + 3 * kKpBins, st[3], 3, s, &box);
-  if (blockIdx.x == 0 && t == 0) st[4] = cur;
-  const uint32_t kth = cur.all ? 0u : cur.prefix;
+  if (strip == 0 && t == 0) st[4] = cur;
+  uint32_t kth;
+  int need;
+  kp_cut(cur, quota, &kth, &need);
   uint32_t k[kKpPerThread];
-  kp_load_keys(key, n, k);
+  kp_load_keys(key, strip, n, k);
   int gt = 0, eq = 0;
 #pragma unroll
   for (int j = 0; j < kKpPerThread; ++j) {
@@ -278,13 +326,18 @@ __global__ __launch_bounds__(kKpThreads) void k_kp_count(const uint32_t* __restr
   if (t == 0) {
     int2 c = part[0];
     for (int w = 1; w < kKpThreads / 64; ++w) { c.x += part[w].x; c.y += part[w].y; }
-    strip_cnt[blockIdx.x] = c;
+    *cnt = c;
   }
 }
 
-__global__ __launch_bounds__(kKpScanThreads) void k_kp_scan(const int2* __restrict__ strip_cnt, int n_strips,
-                                                            const KpSel* __restrict__ st, const uint32_t* __restrict__ n_corners,
-                                                            int2* __restrict__ strip_off, int K, gcs_keypoint_outputs o) {
+__global__ __launch_bounds__(kKpThreads) void k_kp_count(const uint32_t* __restrict__ key, int n, int K,
+                                                         const uint32_t* __restrict__ ghist, KpSel* __restrict__ st,
+                                                         int2* __restrict__ strip_cnt) {
+  kp_count_strip(key, blockIdx.x, n, K, ghist, st, strip_cnt + blockIdx.x);
+}
+
+// exclusive offsets of the strips' counts, by one workgroup of kKpScanThreads
+__device__ __forceinline__ void kp_scan_strips(const int2* __restrict__ strip_cnt, int n_strips, int2* __restrict__ strip_off) {
   __shared__ int sg[kKpScanThreads], se[kKpScanThreads];
   const int t = threadIdx.x;
   const int per = (n_strips + kKpScanThreads - 1) / kKpScanThreads;
@@ -304,6 +357,13 @@ __global__ __launch_bounds__(kKpScanThreads) void k_kp_scan(const int2* __restri
     strip_off[i] = make_int2(g, e);
     g += strip_cnt[i].x; e += strip_cnt[i].y;
   }
+}
+
+__global__ __launch_bounds__(kKpScanThreads) void k_kp_scan(const int2* __restrict__ strip_cnt, int n_strips,
+                                                            const KpSel* __restrict__ st, const uint32_t* __restrict__ n_corners,
+                                                            int2* __restrict__ strip_off, int K, gcs_keypoint_outputs o) {
+  const int t = threadIdx.x;
+  kp_scan_strips(strip_cnt, n_strips, strip_off);
   const KpSel cur = st[4];
   const int n_kp = cur.all ? cur.total : K;
   if (t == 0) {
@@ -315,16 +375,22 @@ __global__ __launch_bounds__(kKpScanThreads) void k_kp_scan(const int2* __restri
   for (int i = n_kp + t; i < K; i += kKpScanThreads) o.kp_u[i] = o.kp_v[i] = o.kp_response[i] = NAN;
 }
 
-__global__ __launch_bounds__(kKpThreads) void k_kp_emit(const uint32_t* __restrict__ key, int n, int W,
-                                                        const KpSel* __restrict__ st, const int2* __restrict__ strip_off,
-                                                        int K, gcs_keypoint_outputs o) {
+// Where a kept pixel goes.  The single-level detector: its own coordinates.  A pyramid level of size Wl x Hl under
+// a W0 x H0 image: the level-0 coordinates of the pixel's centre, and the level.
+struct KpPlace {
+  int Wl, Hl, W0, H0, level;
+  int32_t* kp_level;   // null: the single-level detector
+};
+
+// One strip of a key image n keys long and Wl wide: the kept pixels in raster order at rows first + (the strip's
+// offsets `base` among the keys above and equal to kth); rows from K on are not written.
+__device__ __forceinline__ void kp_emit_strip(const uint32_t* __restrict__ key, int strip, int n, uint32_t kth, int need,
+                                              int2 base, int first, int K, float* __restrict__ kp_u, float* __restrict__ kp_v,
+                                              float* __restrict__ kp_response, const KpPlace pl) {
   __shared__ int2 part[kKpThreads / 64];
   const int t = threadIdx.x;
-  const KpSel cur = st[4];
-  const uint32_t kth = cur.all ? 0u : cur.prefix;
-  const int need = cur.all ? 0 : cur.rem;   // of the keys equal to kth, the first `need` in raster order are kept
   uint32_t k[kKpPerThread];
-  const int i0 = kp_load_keys(key, n, k);
+  const int i0 = kp_load_keys(key, strip, n, k);
   int gt = 0, eq = 0;
 #pragma unroll
   for (int j = 0; j < kKpPerThread; ++j) {
@@ -334,23 +400,198 @@ __global__ __launch_bounds__(kKpThreads) void k_kp_emit(const uint32_t* __restri
   const int ig = kp_wave_incl(gt), ie = kp_wave_incl(eq);
   if ((t & 63) == 63) part[t >> 6] = make_int2(ig, ie);
   __syncthreads();
-  int2 base = strip_off[blockIdx.x];
   for (int w = 0; w < (t >> 6); ++w) { base.x += part[w].x; base.y += part[w].y; }
   int g = base.x + ig - gt, e = base.y + ie - eq;   // keys above / equal to kth before this thread's, in raster order
 #pragma unroll
   for (int j = 0; j < kKpPerThread; ++j) {
     const bool above = k[j] > kth, tie = k[j] == kth;
     if (above || (tie && e < need)) {
-      const int pos = g + min(e, need), i = i0 + j;
+      const int pos = first + g + min(e, need), i = i0 + j;
       if (pos < K) {
-        o.kp_u[pos] = (float)(i % W);
-        o.kp_v[pos] = (float)(i / W);
-        o.kp_response[pos] = __uint_as_float(kp_bits_of_key(k[j]));
+        if (pl.kp_level) {
+          kp_u[pos] = kp_level0_coord(i % pl.Wl, pl.W0, pl.Wl);
+          kp_v[pos] = kp_level0_coord(i / pl.Wl, pl.H0, pl.Hl);
+          pl.kp_level[pos] = pl.level;
+        } else {
+          kp_u[pos] = (float)(i % pl.Wl);
+          kp_v[pos] = (float)(i / pl.Wl);
+        }
+        kp_response[pos] = __uint_as_float(kp_bits_of_key(k[j]));
       }
     }
     g += above;
     e += tie;
   }
+}
+
+__global__ __launch_bounds__(kKpThreads) void k_kp_emit(const uint32_t* __restrict__ key, int n, int W,
+                                                        const KpSel* __restrict__ st, const int2* __restrict__ strip_off,
+                                                        int K, gcs_keypoint_outputs o) {
+  uint32_t kth;
+  int need;   // of the keys equal to kth, the first `need` in raster order are kept
+  kp_cut(st[4], K, &kth, &need);
+  const KpPlace pl = {W, 0, 0, 0, 0, nullptr};
+  kp_emit_strip(key, blockIdx.x, n, kth, need, strip_off[blockIdx.x], 0, K, o.kp_u, o.kp_v, o.kp_response, pl);
+}
+
+// ---- the pyramid (gcs_detect_keypoints_pyramid)
+
+// The level table of the packed workspace.  The grey and score images of the levels follow one another, each
+// level's first pixel on a multiple of 256 (a resample workgroup then has one level); the key image likewise
+// with every level on a strip boundary, so a strip has one level.  A level without pixels has no tiles and no
+// strips.  [n .. 8] of the three running tables hold the totals.
+struct KpLevels {
+  int32_t n;
+  int32_t W[kKpMaxLevels], H[kKpMaxLevels], quota[kKpMaxLevels], tiles_x[kKpMaxLevels];
+  int32_t tile0[kKpMaxLevels + 1], strip0[kKpMaxLevels + 1], block0[kKpMaxLevels + 1];   // block: 256 pixels
+};
+
+// the level of tile / strip / block idx: the last one that starts at or before it
+__device__ inline int kp_level_at(const int32_t* first, int n, int idx) {
+  int l = 0;
+#pragma unroll
+  for (int m = 1; m < kKpMaxLevels; ++m) l += (m < n && idx >= first[m]);
+  return l;
+}
+// a[l] by selects, so that the table stays in scalar registers
+template <int N>
+__device__ inline int kp_pick(const int32_t (&a)[N], int l) {
+  int v = a[0];
+#pragma unroll
+  for (int m = 1; m < N; ++m) v = l >= m ? a[m] : v;
+  return v;
+}
+
+// Pixel (x, y) of the level Wl x Hl wide of a W x H image: the exact pixel-area mean of the grey values under
+// it, rounded half up.  Only pixels of [0, W) x [0, H) are read, byte by byte.
+template <int CH>
+GCS_HD int kp_resample_pixel(const uint8_t* __restrict__ img, int64_t pitch, int W, int H, int Wl, int Hl, int x, int y) {
+  const int j0 = kp_src_first(x, W, Wl), j1 = kp_src_last(x, W, Wl);
+  const int i0 = kp_src_first(y, H, Hl), i1 = kp_src_last(y, H, Hl);
+  int64_t sum = 0;
+  for (int i = i0; i <= i1; ++i) {
+    const uint8_t* row = img + (int64_t)i * pitch;
+    int64_t rs = 0;
+    for (int j = j0; j <= j1; ++j) {
+      const int g = CH == 3 ? kp_grey(row[3 * (int64_t)j], row[3 * (int64_t)j + 1], row[3 * (int64_t)j + 2]) : row[j];
+      rs += kp_overlap(x, j, W, Wl) * g;
+    }
+    sum += kp_overlap(y, i, H, Hl) * rs;
+  }
+  const int64_t area = (int64_t)W * H;
+  return kp_area_mean(sum, area, kp_area_narrow(area));
+}
+
+// every level's grey image from the input, one thread per pixel of the packed image; level 0 is step 1 itself
+template <int CH>
+__global__ __launch_bounds__(kKpThreads) void k_kpp_resample(const uint8_t* __restrict__ img, int64_t pitch, const KpLevels lv,
+                                                             uint8_t* __restrict__ grey_out) {
+  const int l = kp_level_at(lv.block0, lv.n, blockIdx.x);
+  const int Wl = kp_pick(lv.W, l), Hl = kp_pick(lv.H, l);
+  const int local = (blockIdx.x - kp_pick(lv.block0, l)) * kKpThreads + threadIdx.x;
+  if (local >= Wl * Hl) return;
+  const int x = local % Wl, y = local / Wl;
+  int g;
+  if (l == 0) {
+    const uint8_t* p = img + (int64_t)y * pitch + CH * (int64_t)x;
+    g = CH == 3 ? kp_grey(p[0], p[1], p[2]) : p[0];
+  } else {
+    g = kp_resample_pixel<CH>(img, pitch, lv.W[0], lv.H[0], Wl, Hl, x, y);
+  }
+  grey_out[(size_t)blockIdx.x * kKpThreads + threadIdx.x] = (uint8_t)g;
+}
+
+// k_kp_score over the tiles of all levels, from the packed grey image
+__global__ __launch_bounds__(kKpThreads) void k_kpp_score(const uint8_t* __restrict__ grey_in, const KpLevels lv, int threshold,
+                                                          uint8_t* __restrict__ score_out, uint32_t* __restrict__ n_corners) {
+  const int l = kp_level_at(lv.tile0, lv.n, blockIdx.x);
+  const int Wl = kp_pick(lv.W, l), Hl = kp_pick(lv.H, l), tx = kp_pick(lv.tiles_x, l);
+  const int tile = blockIdx.x - kp_pick(lv.tile0, l);
+  const size_t px = (size_t)kp_pick(lv.block0, l) * kKpThreads;
+  kp_score_tile<1, false>(grey_in + px, Wl, Wl, Hl, threshold, nullptr, score_out + px, n_corners + l,
+                          (tile % tx) * kKpTileW, (tile / tx) * kKpTileH);
+}
+
+// k_kp_response over the tiles of all levels; ghist: per level 4 x 256 bins
+__global__ __launch_bounds__(kKpThreads) void k_kpp_response(const uint8_t* __restrict__ score, const uint8_t* __restrict__ grey,
+                                                             const KpLevels lv, int edge, double harris_k,
+                                                             uint32_t* __restrict__ key, uint32_t* __restrict__ ghist) {
+  const int l = kp_level_at(lv.tile0, lv.n, blockIdx.x);
+  const int Wl = kp_pick(lv.W, l), Hl = kp_pick(lv.H, l), tx = kp_pick(lv.tiles_x, l);
+  const int tile = blockIdx.x - kp_pick(lv.tile0, l);
+  const size_t px = (size_t)kp_pick(lv.block0, l) * kKpThreads;
+  kp_response_tile(score + px, grey + px, Wl, Hl, edge, harris_k, key + (size_t)kp_pick(lv.strip0, l) * kKpStrip,
+                   ghist + l * 4 * kKpBins, (tile % tx) * kKpTileW, (tile / tx) * kKpTileH);
+}
+
+// The select, segmented: strip blockIdx.x belongs to one level, whose histograms, state (st + 5 l) and quota it
+// uses.  A quota of 0 runs the select for rank 1 and is cut to nothing afterwards (kp_cut).
+__global__ __launch_bounds__(kKpThreads) void k_kpp_hist(const uint32_t* __restrict__ key, const KpLevels lv, int pass,
+                                                         uint32_t* __restrict__ ghist, KpSel* __restrict__ st) {
+  const int l = kp_level_at(lv.strip0, lv.n, blockIdx.x), first = kp_pick(lv.strip0, l);
+  kp_hist_strip(key + (size_t)first * kKpStrip, blockIdx.x - first, kp_pick(lv.W, l) * kp_pick(lv.H, l),
+                max(kp_pick(lv.quota, l), 1), pass, ghist + l * 4 * kKpBins, st + 5 * l);
+}
+
+__global__ __launch_bounds__(kKpThreads) void k_kpp_count(const uint32_t* __restrict__ key, const KpLevels lv,
+                                                          const uint32_t* __restrict__ ghist, KpSel* __restrict__ st,
+                                                          int2* __restrict__ strip_cnt) {
+  const int l = kp_level_at(lv.strip0, lv.n, blockIdx.x), first = kp_pick(lv.strip0, l);
+  kp_count_strip(key + (size_t)first * kKpStrip, blockIdx.x - first, kp_pick(lv.W, l) * kp_pick(lv.H, l),
+                 kp_pick(lv.quota, l), ghist + l * 4 * kKpBins, st + 5 * l, strip_cnt + blockIdx.x);
+}
+
+// One workgroup over all levels' strips: the offsets run through the levels, so a strip's offset within its
+// level is its own less its level's first strip's.  Then each level's counts, its first output row
+// (level_row), the totals and the padding.
+__global__ __launch_bounds__(kKpScanThreads) void k_kpp_scan(const int2* __restrict__ strip_cnt, const KpLevels lv,
+                                                             const KpSel* __restrict__ st, const uint32_t* __restrict__ n_corners,
+                                                             int2* __restrict__ strip_off, int32_t* __restrict__ level_row, int K,
+                                                             gcs_keypoint_pyramid_outputs o) {
+  __shared__ int n_all;
+  const int t = threadIdx.x;
+  kp_scan_strips(strip_cnt, lv.strip0[kKpMaxLevels], strip_off);
+  if (t == 0) {
+    int row = 0, survivors = 0, corners = 0;
+#pragma unroll
+    for (int l = 0; l < kKpMaxLevels; ++l) {
+      int32_t c[4] = {0, 0, 0, l < lv.n ? lv.quota[l] : 0};
+      if (l < lv.n && lv.strip0[l + 1] > lv.strip0[l]) {   // a level without pixels has no state
+        const KpSel cur = st[5 * l + 4];
+        c[0] = kp_kept(cur, lv.quota[l]);
+        c[1] = cur.total;
+        c[2] = (int32_t)n_corners[l];
+      }
+      level_row[l] = row;
+      for (int j = 0; j < 4; ++j) o.level_counts[4 * l + j] = c[j];
+      row += c[0]; survivors += c[1]; corners += c[2];
+    }
+    o.counts[0] = row;
+    o.counts[1] = survivors;
+    o.counts[2] = corners;
+    o.counts[3] = lv.n;
+    n_all = row;
+  }
+  __syncthreads();
+  for (int i = n_all + t; i < K; i += kKpScanThreads) {
+    o.kp_u[i] = o.kp_v[i] = o.kp_response[i] = NAN;
+    o.kp_level[i] = -1;
+  }
+}
+
+__global__ __launch_bounds__(kKpThreads) void k_kpp_emit(const uint32_t* __restrict__ key, const KpLevels lv,
+                                                         const KpSel* __restrict__ st, const int2* __restrict__ strip_off,
+                                                         const int32_t* __restrict__ level_row, int K,
+                                                         gcs_keypoint_pyramid_outputs o) {
+  const int l = kp_level_at(lv.strip0, lv.n, blockIdx.x), first = kp_pick(lv.strip0, l);
+  const int Wl = kp_pick(lv.W, l), Hl = kp_pick(lv.H, l);
+  uint32_t kth;
+  int need;
+  kp_cut(st[5 * l + 4], kp_pick(lv.quota, l), &kth, &need);
+  const int2 mine = strip_off[blockIdx.x], head = strip_off[first];
+  const KpPlace pl = {Wl, Hl, lv.W[0], lv.H[0], l, o.kp_level};
+  kp_emit_strip(key + (size_t)first * kKpStrip, blockIdx.x - first, Wl * Hl, kth, need,
+                make_int2(mine.x - head.x, mine.y - head.y), level_row[l], K, o.kp_u, o.kp_v, o.kp_response, pl);
 }
 
 // ---- checks and the host build
@@ -376,6 +617,108 @@ const char* kp_check_call(const gcs_keypoint_config& c, const gcs_keypoint_input
   return nullptr;
 }
 
+const char* kp_check_pyramid_config(const gcs_keypoint_pyramid_config* c) {
+  if (!c) return "null config";
+  const gcs_keypoint_config six = {c->fast_threshold, c->edge_threshold, c->max_keypoints, c->max_width,
+                                   c->max_height, c->harris_k, c->device};
+  if (const char* m = kp_check_config(&six)) return m;
+  if (c->n_levels < 1 || c->n_levels > kKpMaxLevels) return "n_levels outside [1, 8]";
+  if (c->scale_den < 1 || c->scale_num <= c->scale_den || c->scale_num > 2 * c->scale_den || c->scale_num > kKpMaxScaleNum)
+    return "scale_num / scale_den outside (1, 2], or scale_num above 64";
+  return nullptr;
+}
+
+const char* kp_check_pyramid_call(const gcs_keypoint_pyramid_config& c, const gcs_keypoint_inputs* in,
+                                  const gcs_keypoint_pyramid_outputs* o) {
+  if (!in || !o) return "null inputs or outputs";
+  if (in->channels != 1 && in->channels != 3) return "channels is 1 (gray8) or 3 (rgb8)";
+  if (in->width < 1 || in->height < 1 || in->width > c.max_width || in->height > c.max_height)
+    return "width or height below 1 or above the context's capacity";
+  if (in->pitch < (int64_t)in->channels * in->width) return "pitch below a row";
+  if (!in->image || !o->kp_u || !o->kp_v || !o->kp_response || !o->kp_level || !o->counts || !o->level_counts)
+    return "null array";
+  return nullptr;
+}
+
+// the level table of a W x H image (W H <= 2^28, so every level's pixel count stays in int32)
+KpLevels kp_levels(const gcs_keypoint_pyramid_config& c, int W, int H) {
+  KpLevels lv{};
+  lv.n = c.n_levels;
+  kp_quotas(c.max_keypoints, c.n_levels, c.scale_num, c.scale_den, lv.quota);
+  for (int l = 0; l < kKpMaxLevels; ++l) {
+    int64_t px = 0;
+    if (l < lv.n) {
+      lv.W[l] = kp_level_size(W, c.scale_num, c.scale_den, l);
+      lv.H[l] = kp_level_size(H, c.scale_num, c.scale_den, l);
+      if (lv.W[l] >= 1 && lv.H[l] >= 1) px = (int64_t)lv.W[l] * lv.H[l];
+    }
+    lv.tiles_x[l] = px ? (lv.W[l] + kKpTileW - 1) / kKpTileW : 0;
+    lv.tile0[l + 1] = lv.tile0[l] + (px ? lv.tiles_x[l] * ((lv.H[l] + kKpTileH - 1) / kKpTileH) : 0);
+    lv.strip0[l + 1] = lv.strip0[l] + (int32_t)((px + kKpStrip - 1) / kKpStrip);
+    lv.block0[l + 1] = lv.block0[l] + (int32_t)((px + kKpThreads - 1) / kKpThreads);
+  }
+  return lv;
+}
+
+// Steps 2-6 on a W x H grey image on the host: the kept pixels' raster indices and response bits in raster
+// order; counts: n_keypoints, n_survivors, n_corners.  K = 0 keeps nothing.
+void kp_host_level(const uint8_t* grey, int W, int H, int threshold, int edge, int K, double harris_k,
+                   std::vector<int32_t>* kept_at, std::vector<uint32_t>* kept_bits, int32_t counts[3]) {
+  const size_t n = (size_t)W * (size_t)H;
+  std::vector<uint8_t> score(n, 0);
+  int32_t n_corners = 0;
+  for (int y = kKpFrame; y < H - kKpFrame; ++y)
+    for (int x = kKpFrame; x < W - kKpFrame; ++x) {
+      const int s = kp_fast_score(&grey[(size_t)y * W + x], W, threshold);
+      score[(size_t)y * W + x] = (uint8_t)s;
+      n_corners += s > 0;
+    }
+  std::vector<uint32_t> keys;   // the survivors, in raster order
+  std::vector<int32_t> at;
+  for (int y = edge; y < H - edge; ++y)
+    for (int x = edge; x < W - edge; ++x) {
+      const uint8_t* c = &score[(size_t)y * W + x];   // edge >= 4: the neighbours are inside
+      const int s = c[0];
+      if (!(s > 0 && s > c[-W - 1] && s > c[-W] && s > c[-W + 1] && s > c[-1] && s > c[1] && s > c[W - 1] && s > c[W] &&
+            s > c[W + 1]))
+        continue;
+      int64_t a = 0, b = 0, cc = 0;
+      for (int l = 0; l < kKpBlock * kKpBlock; ++l) {
+        int ix, iy;
+        kp_sobel(&grey[(size_t)(y + l / kKpBlock - kKpBlock / 2) * W + (x + l % kKpBlock - kKpBlock / 2)], W, &ix, &iy);
+        a += ix * ix; b += iy * iy; cc += ix * iy;
+      }
+      float r = kp_response(a, b, cc, harris_k);
+      uint32_t bits;
+      memcpy(&bits, &r, 4);
+      keys.push_back(kp_key_of_bits(bits));
+      at.push_back(y * W + x);
+    }
+  const int total = (int)keys.size();
+  uint32_t kth = K > 0 ? 0u : 0xffffffffu;   // (no finite response has the key 0xffffffff)
+  int need = 0;
+  if (K > 0 && total > K) {   // the K-th largest key; of the keys equal to it the first `need` in raster order stay
+    std::vector<uint32_t> sorted(keys);
+    std::nth_element(sorted.begin(), sorted.begin() + (K - 1), sorted.end(), std::greater<uint32_t>());
+    kth = sorted[K - 1];
+    int above = 0;
+    for (uint32_t k : keys) above += k > kth;
+    need = K - above;
+  }
+  int e = 0;
+  for (int i = 0; i < total; ++i) {
+    const bool tie = keys[i] == kth;
+    if (keys[i] > kth || (tie && e < need)) {
+      kept_at->push_back(at[i]);
+      kept_bits->push_back(kp_bits_of_key(keys[i]));
+    }
+    e += tie;
+  }
+  counts[0] = (int32_t)kept_at->size();
+  counts[1] = total;
+  counts[2] = n_corners;
+}
+
 }  // namespace
 }  // namespace gcs
 
@@ -391,7 +734,28 @@ struct gcs_keypoint_ctx {
   KpWork w{};
 };
 
+struct gcs_keypoint_pyramid_ctx {
+  gcs_keypoint_pyramid_config cfg{};
+  std::string err;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  void* d_mem = nullptr;
+  size_t clear_bytes = 0;         // every level's histograms and n_corners, zeroed at the head of every call
+  int cap_blocks = 0, cap_strips = 0;   // the packed workspace: 256-pixel blocks and 2048-key strips
+  KpWork w{};                     // hist: per level 4 x 256 bins, then n_corners per level; st: per level [1..4]
+  int32_t* level_row = nullptr;   // the first output row of every level
+};
+
 namespace {
+int kpp_fail(gcs_keypoint_pyramid_ctx* c, int code, const std::string& m) {
+  if (c) c->err = m;
+  return code;
+}
+#define KPPCHK(ctx, expr)                                                                          \
+  do {                                                                                            \
+    hipError_t _e = (expr);                                                                       \
+    if (_e != hipSuccess) return kpp_fail((ctx), GCS_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
+  } while (0)
 int kp_fail(gcs_keypoint_ctx* c, int code, const std::string& m) {
   if (c) c->err = m;
   return code;
@@ -473,67 +837,26 @@ int gcs_detect_keypoints_host(const gcs_keypoint_config* cfg, const gcs_keypoint
   if (kp_check_config(cfg) || kp_check_call(*cfg, in, out)) return GCS_ERR_ARG;
   const int W = in->width, H = in->height, K = cfg->max_keypoints, edge = cfg->edge_threshold;
   const size_t n = (size_t)W * (size_t)H;
-  std::vector<uint8_t> grey(n), score(n, 0);
+  std::vector<uint8_t> grey(n);
   for (int y = 0; y < H; ++y) {
     const uint8_t* row = in->image + (int64_t)y * in->pitch;
     for (int x = 0; x < W; ++x)
       grey[(size_t)y * W + x] = in->channels == 3 ? (uint8_t)kp_grey(row[3 * x], row[3 * x + 1], row[3 * x + 2]) : row[x];
   }
-  int32_t n_corners = 0;
-  for (int y = kKpFrame; y < H - kKpFrame; ++y)
-    for (int x = kKpFrame; x < W - kKpFrame; ++x) {
-      const int s = kp_fast_score(&grey[(size_t)y * W + x], W, cfg->fast_threshold);
-      score[(size_t)y * W + x] = (uint8_t)s;
-      n_corners += s > 0;
-    }
-  std::vector<uint32_t> keys;   // the survivors, in raster order
   std::vector<int32_t> at;
-  for (int y = edge; y < H - edge; ++y)
-    for (int x = edge; x < W - edge; ++x) {
-      const uint8_t* c = &score[(size_t)y * W + x];   // edge >= 4: the neighbours are inside
-      const int s = c[0];
-      if (!(s > 0 && s > c[-W - 1] && s > c[-W] && s > c[-W + 1] && s > c[-1] && s > c[1] && s > c[W - 1] && s > c[W] &&
-            s > c[W + 1]))
-        continue;
-      int64_t a = 0, b = 0, cc = 0;
-      for (int l = 0; l < kKpBlock * kKpBlock; ++l) {
-        int ix, iy;
-        kp_sobel(&grey[(size_t)(y + l / kKpBlock - kKpBlock / 2) * W + (x + l % kKpBlock - kKpBlock / 2)], W, &ix, &iy);
-        a += ix * ix; b += iy * iy; cc += ix * iy;
-      }
-      float r = kp_response(a, b, cc, cfg->harris_k);
-      uint32_t bits;
-      memcpy(&bits, &r, 4);
-      keys.push_back(kp_key_of_bits(bits));
-      at.push_back(y * W + x);
-    }
-  const int total = (int)keys.size();
-  uint32_t kth = 0;
-  int need = 0;
-  if (total > K) {   // the K-th largest key; of the keys equal to it the first `need` in raster order stay
-    std::vector<uint32_t> sorted(keys);
-    std::nth_element(sorted.begin(), sorted.begin() + (K - 1), sorted.end(), std::greater<uint32_t>());
-    kth = sorted[K - 1];
-    int above = 0;
-    for (uint32_t k : keys) above += k > kth;
-    need = K - above;
-  }
-  int m = 0, e = 0;
-  for (int i = 0; i < total; ++i) {
-    const bool tie = keys[i] == kth;
-    if (keys[i] > kth || (tie && e < need)) {
-      const uint32_t bits = kp_bits_of_key(keys[i]);
-      out->kp_u[m] = (float)(at[i] % W);
-      out->kp_v[m] = (float)(at[i] / W);
-      memcpy(&out->kp_response[m], &bits, 4);
-      ++m;
-    }
-    e += tie;
+  std::vector<uint32_t> bits;
+  int32_t counts[3];
+  kp_host_level(grey.data(), W, H, cfg->fast_threshold, edge, K, cfg->harris_k, &at, &bits, counts);
+  const int m = counts[0];
+  for (int i = 0; i < m; ++i) {
+    out->kp_u[i] = (float)(at[i] % W);
+    out->kp_v[i] = (float)(at[i] / W);
+    memcpy(&out->kp_response[i], &bits[i], 4);
   }
   for (int i = m; i < K; ++i) out->kp_u[i] = out->kp_v[i] = out->kp_response[i] = NAN;
   out->counts[0] = m;
-  out->counts[1] = total;
-  out->counts[2] = n_corners;
+  out->counts[1] = counts[1];
+  out->counts[2] = counts[2];
   out->counts[3] = 0;
   return GCS_OK;
 }
@@ -558,12 +881,184 @@ int gcs_detect_keypoints(gcs_keypoint_ctx* c, const gcs_keypoint_inputs* in, gcs
   const int n_strips = (n + kKpStrip - 1) / kKpStrip;
   for (int pass = 1; pass <= 3; ++pass)
     hipLaunchKernelGGL(k_kp_hist, dim3(n_strips), threads, 0, c->stream, w.key, n, K, pass, w.hist, w.st);
-  hipLaunchKernelGGL(k_kp_count, dim3(n_strips), threads, 0, c->stream, w.key, n, w.hist, w.st, w.strip_cnt);
+  hipLaunchKernelGGL(k_kp_count, dim3(n_strips), threads, 0, c->stream, w.key, n, K, w.hist, w.st, w.strip_cnt);
   const gcs_keypoint_outputs o = *out;
   hipLaunchKernelGGL(k_kp_scan, dim3(1), dim3(kKpScanThreads), 0, c->stream, w.strip_cnt, n_strips, w.st, n_corners,
                      w.strip_off, K, o);
   hipLaunchKernelGGL(k_kp_emit, dim3(n_strips), threads, 0, c->stream, w.key, n, W, w.st, w.strip_off, K, o);
   KPCHK(c, hipGetLastError());
+  return GCS_OK;
+}
+
+// ---- the pyramid
+
+int gcs_keypoint_pyramid_config_defaults(gcs_keypoint_pyramid_config* c) {
+  if (!c) return GCS_ERR_ARG;
+  gcs_keypoint_config six;
+  gcs_keypoint_config_defaults(&six);
+  memset(c, 0, sizeof(*c));
+  c->fast_threshold = six.fast_threshold;
+  c->edge_threshold = six.edge_threshold;
+  c->max_keypoints = six.max_keypoints;
+  c->max_width = six.max_width;
+  c->max_height = six.max_height;
+  c->harris_k = six.harris_k;
+  c->n_levels = 8;
+  c->scale_num = 6;
+  c->scale_den = 5;
+  c->device = 0;
+  return GCS_OK;
+}
+
+int gcs_keypoint_pyramid_layout(const gcs_keypoint_pyramid_config* cfg, int32_t width, int32_t height,
+                                int32_t out[GCS_KEYPOINT_MAX_LEVELS][3]) {
+  if (kp_check_pyramid_config(cfg) || !out || width < 1 || height < 1 || (int64_t)width * height > kKpMaxPixels)
+    return GCS_ERR_ARG;
+  const KpLevels lv = kp_levels(*cfg, width, height);
+  for (int l = 0; l < kKpMaxLevels; ++l) {
+    out[l][0] = lv.W[l];
+    out[l][1] = lv.H[l];
+    out[l][2] = lv.quota[l];
+  }
+  return GCS_OK;
+}
+
+const char* gcs_keypoint_pyramid_last_error(const gcs_keypoint_pyramid_ctx* c) {
+  return c ? c->err.c_str() : "null keypoint pyramid context";
+}
+
+int gcs_keypoint_pyramid_ctx_destroy(gcs_keypoint_pyramid_ctx* c) {
+  if (!c) return GCS_OK;
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->d_mem) (void)hipFree(c->d_mem);
+  delete c;
+  return GCS_OK;
+}
+
+int gcs_keypoint_pyramid_ctx_create(const gcs_keypoint_pyramid_config* cfg, gcs_keypoint_pyramid_ctx** out) {
+  if (!cfg || !out) return GCS_ERR_ARG;
+  *out = nullptr;
+  if (kp_check_pyramid_config(cfg)) return GCS_ERR_ARG;
+  auto* c = new gcs_keypoint_pyramid_ctx();
+  c->cfg = *cfg;
+  c->device = cfg->device;
+  // A level's size grows with the image's, so the table of max_width x max_height bounds every image's.
+  const KpLevels cap = kp_levels(*cfg, cfg->max_width, cfg->max_height);
+  c->cap_blocks = cap.block0[kKpMaxLevels];
+  c->cap_strips = cap.strip0[kKpMaxLevels];
+  const size_t px = (size_t)c->cap_blocks * kKpThreads, strips = (size_t)c->cap_strips;
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  c->clear_bytes = sizeof(uint32_t) * (kKpMaxLevels * 4 * kKpBins + kKpMaxLevels);
+  const size_t z_hist = up(c->clear_bytes), z_st = up(sizeof(KpSel) * 5 * kKpMaxLevels), z_row = up(sizeof(int32_t) * kKpMaxLevels);
+  const size_t z_px = up(px), z_key = up(strips * kKpStrip * sizeof(uint32_t)), z_strip = up(strips * sizeof(int2));
+  if (hipSetDevice(cfg->device) != hipSuccess ||
+      hipMalloc(&c->d_mem, z_hist + z_st + z_row + 2 * z_px + z_key + 2 * z_strip) != hipSuccess) {
+    gcs_keypoint_pyramid_ctx_destroy(c);
+    return GCS_ERR_HIP;
+  }
+  uint8_t* p = (uint8_t*)c->d_mem;
+  c->w.hist = (uint32_t*)p; p += z_hist;
+  c->w.st = (KpSel*)p; p += z_st;
+  c->level_row = (int32_t*)p; p += z_row;
+  c->w.key = (uint32_t*)p; p += z_key;
+  c->w.strip_cnt = (int2*)p; p += z_strip;
+  c->w.strip_off = (int2*)p; p += z_strip;
+  c->w.grey = p; p += z_px;
+  c->w.score = p;
+  *out = c;
+  return GCS_OK;
+}
+
+int gcs_keypoint_pyramid_ctx_set_stream(gcs_keypoint_pyramid_ctx* c, void* stream) {
+  if (!c) return GCS_ERR_ARG;
+  hipStream_t ns = (hipStream_t)stream;
+  if (ns == c->stream) return GCS_OK;
+  KPPCHK(c, hipSetDevice(c->device));
+  KPPCHK(c, hipStreamSynchronize(c->stream));  // the workspace is shared: the old stream's work completes first
+  c->stream = ns;
+  return GCS_OK;
+}
+
+int gcs_detect_keypoints_pyramid_host(const gcs_keypoint_pyramid_config* cfg, const gcs_keypoint_inputs* in,
+                                      gcs_keypoint_pyramid_outputs* out) {
+  if (kp_check_pyramid_config(cfg) || kp_check_pyramid_call(*cfg, in, out)) return GCS_ERR_ARG;
+  const int W = in->width, H = in->height, K = cfg->max_keypoints;
+  const KpLevels lv = kp_levels(*cfg, W, H);
+  int32_t sum[3] = {0, 0, 0};
+  int m = 0;
+  std::vector<uint8_t> grey;
+  for (int l = 0; l < kKpMaxLevels; ++l) {
+    int32_t counts[3] = {0, 0, 0};
+    if (lv.strip0[l + 1] > lv.strip0[l]) {   // the level has pixels
+      const int Wl = lv.W[l], Hl = lv.H[l];
+      grey.assign((size_t)Wl * Hl, 0);
+      for (int y = 0; y < Hl; ++y)
+        for (int x = 0; x < Wl; ++x) {
+          int g;
+          if (l == 0) {
+            const uint8_t* p = in->image + (int64_t)y * in->pitch + (int64_t)in->channels * x;
+            g = in->channels == 3 ? kp_grey(p[0], p[1], p[2]) : p[0];
+          } else {
+            g = in->channels == 3 ? kp_resample_pixel<3>(in->image, in->pitch, W, H, Wl, Hl, x, y)
+                                  : kp_resample_pixel<1>(in->image, in->pitch, W, H, Wl, Hl, x, y);
+          }
+          grey[(size_t)y * Wl + x] = (uint8_t)g;
+        }
+      std::vector<int32_t> at;
+      std::vector<uint32_t> bits;
+      kp_host_level(grey.data(), Wl, Hl, cfg->fast_threshold, cfg->edge_threshold, lv.quota[l], cfg->harris_k, &at, &bits,
+                    counts);
+      for (size_t i = 0; i < at.size() && m < K; ++i, ++m) {   // (the quotas sum to K)
+        out->kp_u[m] = kp_level0_coord(at[i] % Wl, W, Wl);
+        out->kp_v[m] = kp_level0_coord(at[i] / Wl, H, Hl);
+        memcpy(&out->kp_response[m], &bits[i], 4);
+        out->kp_level[m] = l;
+      }
+    }
+    for (int j = 0; j < 3; ++j) {
+      out->level_counts[4 * l + j] = counts[j];
+      sum[j] += counts[j];
+    }
+    out->level_counts[4 * l + 3] = l < lv.n ? lv.quota[l] : 0;
+  }
+  for (int i = m; i < K; ++i) {
+    out->kp_u[i] = out->kp_v[i] = out->kp_response[i] = NAN;
+    out->kp_level[i] = -1;
+  }
+  for (int j = 0; j < 3; ++j) out->counts[j] = sum[j];
+  out->counts[3] = lv.n;
+  return GCS_OK;
+}
+
+int gcs_detect_keypoints_pyramid(gcs_keypoint_pyramid_ctx* c, const gcs_keypoint_inputs* in,
+                                 gcs_keypoint_pyramid_outputs* out) {
+  if (!c) return GCS_ERR_ARG;
+  if (const char* m = kp_check_pyramid_call(c->cfg, in, out)) return kpp_fail(c, GCS_ERR_ARG, m);
+  const KpLevels lv = kp_levels(c->cfg, in->width, in->height);
+  const int n_blocks = lv.block0[kKpMaxLevels], n_tiles = lv.tile0[kKpMaxLevels], n_strips = lv.strip0[kKpMaxLevels];
+  if (n_blocks > c->cap_blocks || n_strips > c->cap_strips) return kpp_fail(c, GCS_ERR_ARG, "the image's levels exceed the workspace");
+  KPPCHK(c, hipSetDevice(c->device));
+  const int K = c->cfg.max_keypoints;
+  const KpWork& w = c->w;
+  uint32_t* n_corners = w.hist + kKpMaxLevels * 4 * kKpBins;
+  KPPCHK(c, hipMemsetAsync(w.hist, 0, c->clear_bytes, c->stream));
+  const dim3 threads(kKpThreads);
+  if (in->channels == 3)
+    hipLaunchKernelGGL(k_kpp_resample<3>, dim3(n_blocks), threads, 0, c->stream, in->image, in->pitch, lv, w.grey);
+  else
+    hipLaunchKernelGGL(k_kpp_resample<1>, dim3(n_blocks), threads, 0, c->stream, in->image, in->pitch, lv, w.grey);
+  hipLaunchKernelGGL(k_kpp_score, dim3(n_tiles), threads, 0, c->stream, w.grey, lv, c->cfg.fast_threshold, w.score, n_corners);
+  hipLaunchKernelGGL(k_kpp_response, dim3(n_tiles), threads, 0, c->stream, w.score, w.grey, lv, c->cfg.edge_threshold,
+                     c->cfg.harris_k, w.key, w.hist);
+  for (int pass = 1; pass <= 3; ++pass)
+    hipLaunchKernelGGL(k_kpp_hist, dim3(n_strips), threads, 0, c->stream, w.key, lv, pass, w.hist, w.st);
+  hipLaunchKernelGGL(k_kpp_count, dim3(n_strips), threads, 0, c->stream, w.key, lv, w.hist, w.st, w.strip_cnt);
+  const gcs_keypoint_pyramid_outputs o = *out;
+  hipLaunchKernelGGL(k_kpp_scan, dim3(1), dim3(kKpScanThreads), 0, c->stream, w.strip_cnt, lv, w.st, n_corners, w.strip_off,
+                     c->level_row, K, o);
+  hipLaunchKernelGGL(k_kpp_emit, dim3(n_strips), threads, 0, c->stream, w.key, lv, w.st, w.strip_off, c->level_row, K, o);
+  KPPCHK(c, hipGetLastError());
   return GCS_OK;
 }
 

@@ -5,6 +5,8 @@
 // every operation rounded on its own and one final rounding to f32.  The pixel readers take a pointer to
 // the centre pixel and the distance between rows in bytes, so that the same code reads an LDS tile on the
 // device and the whole image on the host.
+// Below them the scale pyramid's integer arithmetic (gcs_detect_keypoints_pyramid): level sizes, the area
+// resample's overlap weights, the quotas and the map back to level-0 coordinates.
 #pragma once
 
 #include <stdint.h>
@@ -112,5 +114,60 @@ GCS_HD float kp_response(int64_t a, int64_t b, int64_t c, double harris_k) {
 // the order-preserving map of a float32's bits to uint32; 0 is no finite float's key
 GCS_HD uint32_t kp_key_of_bits(uint32_t b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 GCS_HD uint32_t kp_bits_of_key(uint32_t k) { return (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; }
+
+// ---- the scale pyramid (gcs_detect_keypoints_pyramid): level sizes, area weights, quotas, the coordinate map
+
+constexpr int kKpMaxLevels = 8;
+constexpr int kKpMaxScaleNum = 64;
+
+// b^l for 1 <= b <= 64, 0 <= l <= 7: below 2^43
+GCS_HD int64_t kp_ipow(int b, int l) {
+  int64_t r = 1;
+  for (int i = 0; i < l; ++i) r *= b;
+  return r;
+}
+
+// W_l = (2 W D + N) / (2 N), N = scale_num^l, D = scale_den^l: W D / N rounded half up.  W D can pass 2^63 at
+// the largest widths and denominators, so the quotient is formed in 128 bits.
+GCS_HD int kp_level_size(int W, int scale_num, int scale_den, int l) {
+  const unsigned __int128 N = (unsigned __int128)kp_ipow(scale_num, l), D = (unsigned __int128)kp_ipow(scale_den, l);
+  return (int)((2 * (unsigned __int128)W * D + N) / (2 * N));
+}
+
+// In units of 1 / W_l of a source pixel, destination pixel x covers [x W, (x + 1) W) and source pixel j covers
+// [j W_l, (j + 1) W_l): the integer length of their overlap.  Over j it sums to W.
+GCS_HD int64_t kp_overlap(int x, int j, int W, int W_l) {
+  const int64_t a0 = (int64_t)x * W, a1 = a0 + W, b0 = (int64_t)j * W_l, b1 = b0 + W_l;
+  const int64_t lo = a0 > b0 ? a0 : b0, hi = a1 < b1 ? a1 : b1;
+  return hi > lo ? hi - lo : 0;
+}
+// the first and the last source pixel that destination pixel x overlaps
+GCS_HD int kp_src_first(int x, int W, int W_l) { return (int)(((int64_t)x * W) / W_l); }
+GCS_HD int kp_src_last(int x, int W, int W_l) { return (int)((((int64_t)x + 1) * W - 1) / W_l); }
+
+// I_l = (sum + (W H) / 2) / (W H) of the weighted sum over the footprint; `narrow`: sum + W H / 2 < 2^32
+GCS_HD int kp_area_mean(int64_t sum, int64_t area, bool narrow) {
+  if (narrow) return (int)((uint32_t)(sum + area / 2) / (uint32_t)area);
+  return (int)((uint64_t)(sum + area / 2) / (uint64_t)area);
+}
+GCS_HD bool kp_area_narrow(int64_t area) { return area <= (int64_t)0xffffffffu / 256; }
+
+// quota_l: K w_l / sum w (integer division) with w_l = scale_den^l scale_num^(L - 1 - l) for l >= 1; level 0
+// takes what is left of K
+GCS_HD void kp_quotas(int K, int L, int scale_num, int scale_den, int32_t* quota) {
+  int64_t w[kKpMaxLevels], sum = 0;
+  for (int l = 0; l < L; ++l) sum += w[l] = kp_ipow(scale_den, l) * kp_ipow(scale_num, L - 1 - l);
+  int rest = K;
+  for (int l = 1; l < L; ++l) rest -= quota[l] = (int32_t)(((int64_t)K * w[l]) / sum);
+  quota[0] = rest;
+  for (int l = L; l < kKpMaxLevels; ++l) quota[l] = 0;
+}
+
+// the level-0 coordinate of the centre of pixel x of a level W_l wide: (2 x + 1) W / (2 W_l) - 0.5; the
+// integers are exact, the division and the subtraction are rounded on their own, then once to float32
+GCS_HD float kp_level0_coord(int x, int W, int W_l) {
+  const double q = (double)((2 * (int64_t)x + 1) * W) / (double)(2 * (int64_t)W_l);
+  return (float)(q - 0.5);
+}
 
 }  // namespace gcs

@@ -213,6 +213,19 @@ class GcsKeypointOutputs(C.Structure):
     _fields_ = [("kp_u", C.c_void_p), ("kp_v", C.c_void_p), ("kp_response", C.c_void_p), ("counts", C.c_void_p)]
 
 
+KEYPOINT_MAX_LEVELS = 8
+
+
+class GcsKeypointPyramidConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("fast_threshold", "edge_threshold", "max_keypoints", "max_width",
+                                         "max_height")] + [("harris_k", C.c_double)] + \
+               [(n, C.c_int32) for n in ("n_levels", "scale_num", "scale_den", "device")]
+
+
+class GcsKeypointPyramidOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("kp_u", "kp_v", "kp_response", "kp_level", "counts", "level_counts")]
+
+
 class GcsRenderConfig(C.Structure):
     _fields_ = [("tile_size", C.c_int32), ("max_splats_per_tile", C.c_int32), ("fbm_octaves", C.c_int32),
                 ("fbm_gain", C.c_double), ("opacity_gamma", C.c_double), ("logdet0", C.c_double), ("eps", C.c_double),
@@ -481,6 +494,16 @@ _SIGS = [
     ("gcs_detect_keypoints", C.c_int, [C.c_void_p, C.POINTER(GcsKeypointInputs), C.POINTER(GcsKeypointOutputs)]),
     ("gcs_detect_keypoints_host", C.c_int, [C.POINTER(GcsKeypointConfig), C.POINTER(GcsKeypointInputs),
                                             C.POINTER(GcsKeypointOutputs)]),
+    ("gcs_keypoint_pyramid_config_defaults", C.c_int, [C.POINTER(GcsKeypointPyramidConfig)]),
+    ("gcs_keypoint_pyramid_ctx_create", C.c_int, [C.POINTER(GcsKeypointPyramidConfig), C.POINTER(C.c_void_p)]),
+    ("gcs_keypoint_pyramid_ctx_destroy", C.c_int, [C.c_void_p]),
+    ("gcs_keypoint_pyramid_last_error", C.c_char_p, [C.c_void_p]),
+    ("gcs_keypoint_pyramid_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gcs_detect_keypoints_pyramid", C.c_int, [C.c_void_p, C.POINTER(GcsKeypointInputs),
+                                               C.POINTER(GcsKeypointPyramidOutputs)]),
+    ("gcs_detect_keypoints_pyramid_host", C.c_int, [C.POINTER(GcsKeypointPyramidConfig), C.POINTER(GcsKeypointInputs),
+                                                    C.POINTER(GcsKeypointPyramidOutputs)]),
+    ("gcs_keypoint_pyramid_layout", C.c_int, [C.POINTER(GcsKeypointPyramidConfig), C.c_int32, C.c_int32, C.c_void_p]),
     ("gcs_render_config_defaults", C.c_int, [C.POINTER(GcsRenderConfig)]),
     ("gcs_render_ctx_create", C.c_int, [C.POINTER(GcsRenderConfig), C.POINTER(C.c_void_p)]),
     ("gcs_render_ctx_destroy", C.c_int, [C.c_void_p]),

@@ -793,8 +793,8 @@ int gcs_visual_features_host(const gcs_visfeat_config* cfg, const gcs_visfeat_in
 /* ---------------------------------------------------------------- primitive path: keypoint detector */
 /* Keypoints from an 8-bit image on the GPU, in the form gcs_visfeat_inputs reads.  This detector is the
  * project's own.  It follows the published FAST / ORB recipe, but it claims no parity with cv::ORB: there
- * is no pyramid (ORB's nlevels = 8, scaleFactor = 1.2), there is no orientation, and there are no
- * descriptors.  Everything is exact integer arithmetic except the last step of the response:
+ * is no pyramid here (ORB's nlevels = 8, scaleFactor = 1.2: gcs_detect_keypoints_pyramid, below), there is no
+ * orientation, and there are no descriptors.  Everything is exact integer arithmetic except the last step of the response:
  *  1. grey: gray8 as it is; rgb8 as g = (4899 R + 9617 G + 1868 B + 8192) >> 14.
  *  2. FAST-9/16 score: the ring is the radius-3 Bresenham circle, clockwise from the top: (0,-3) (1,-3)
  *     (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3).
@@ -857,6 +857,77 @@ int gcs_detect_keypoints(gcs_keypoint_ctx* ctx, const gcs_keypoint_inputs* in, g
 /* The same steps on the host (no device, no context): every pointer is a host array. */
 int gcs_detect_keypoints_host(const gcs_keypoint_config* cfg, const gcs_keypoint_inputs* in,
                               gcs_keypoint_outputs* out);
+
+/* Keypoints over a scale pyramid: the detector above on n_levels images, each level with its own share of
+ * max_keypoints, every keypoint in level-0 pixel coordinates (what ORB's nlevels = 8, scaleFactor = 1.2 adds
+ * to the detector front; still no orientation, no descriptors and no parity with cv::ORB).  The definition is
+ * the project's own and is integer-exact wherever the one above is.  With W x H the input, L = n_levels,
+ * K = max_keypoints and the scale factor the rational scale_num / scale_den (no pow, no floating-point
+ * scale anywhere):
+ *  P1. level sizes: with N = scale_num^l and D = scale_den^l, W_l = (2 W D + N) / (2 N) in integer division
+ *      (W D / N rounded half up), H_l likewise.  A level with W_l < 1 or H_l < 1 has no pixels and yields no
+ *      keypoints; that is not an error.
+ *  P2. level images: level 0 is step 1's grey image.  Level l >= 1 is the exact pixel-area resample of level
+ *      0 (not of level l - 1).  Per axis, in units of 1 / W_l of a source pixel, destination pixel x covers
+ *      [x W, (x + 1) W) and source pixel j covers [j W_l, (j + 1) W_l); wx(x, j) is the integer length of
+ *      their overlap (sum over j: W), wy the same with H and H_l, and
+ *      I_l(x, y) = (sum_{j,i} wx(x, j) wy(y, i) I_0(j, i) + (W H) / 2) / (W H) in int64, integer division.
+ *  P3. per level: steps 2-5 above on I_l at W_l x H_l, with the same fast_threshold, the same edge_threshold
+ *      in that level's pixels and the same harris_k.
+ *  P4. quotas: w_l = scale_den^l scale_num^(L - 1 - l); quota_l = (K w_l) / sum(w) (integer division) for
+ *      l >= 1 and quota_0 = K - sum_{l >= 1} quota_l.  Quotas do not depend on the image and an unused share
+ *      is not handed on.  Level l keeps its quota_l best by step 6's rule (response descending, raster index
+ *      y W_l + x ascending, the same tie handling); a quota of 0 keeps nothing.
+ *  P5. output: rows in (level ascending, raster index ascending) order;
+ *      kp_u = (float)((double)((2 x + 1) W) / (double)(2 W_l) - 0.5), kp_v likewise with H: the integers are
+ *      exact, the division and the subtraction are each rounded on their own, then once to float32 (at level
+ *      0 this is x exactly).  kp_response is the level's own response, unscaled; kp_level the row's level.
+ *      Rows [n_keypoints, max_keypoints) are NaN in the three float arrays and -1 in kp_level, so the chain
+ *      into gcs_visual_features with n_keypoints = max_keypoints and no wait works as above.
+ * With n_levels = 1 every byte equals gcs_detect_keypoints' with the same six fields; the level-0 rows equal
+ * gcs_detect_keypoints with max_keypoints = quota_0.  The number of kernel launches of a call does not depend
+ * on n_levels.  max_width x max_height is the capacity for level 0; the other levels' workspace follows from
+ * it.  Calls on one context must be serialised. */
+typedef struct gcs_keypoint_pyramid_ctx gcs_keypoint_pyramid_ctx;
+#define GCS_KEYPOINT_MAX_LEVELS 8
+
+typedef struct {
+  int32_t fast_threshold;        /* the six fields of gcs_keypoint_config, same defaults and ranges */
+  int32_t edge_threshold;
+  int32_t max_keypoints;
+  int32_t max_width, max_height;
+  double harris_k;
+  int32_t n_levels;              /* 8 (ORB's nlevels); 1 .. GCS_KEYPOINT_MAX_LEVELS */
+  int32_t scale_num, scale_den;  /* 6 / 5 (ORB's scaleFactor 1.2); scale_den >= 1,
+                                    scale_den < scale_num <= 2 scale_den, scale_num <= 64 */
+  int32_t device;
+} gcs_keypoint_pyramid_config;
+
+typedef struct {
+  float *kp_u, *kp_v, *kp_response;   /* max_keypoints each */
+  int32_t* kp_level;             /* max_keypoints */
+  int32_t* counts;               /* 4: n_keypoints, n_survivors, n_corners (each summed over the levels), n_levels */
+  int32_t* level_counts;         /* GCS_KEYPOINT_MAX_LEVELS x 4: per level n_keypoints, n_survivors, n_corners,
+                                    quota; rows of levels >= n_levels are zero */
+} gcs_keypoint_pyramid_outputs;
+
+int gcs_keypoint_pyramid_config_defaults(gcs_keypoint_pyramid_config* cfg);
+/* GCS_ERR_ARG, before any device call, for a config outside the ranges above. */
+int gcs_keypoint_pyramid_ctx_create(const gcs_keypoint_pyramid_config* cfg, gcs_keypoint_pyramid_ctx** out);
+int gcs_keypoint_pyramid_ctx_destroy(gcs_keypoint_pyramid_ctx* ctx);
+const char* gcs_keypoint_pyramid_last_error(const gcs_keypoint_pyramid_ctx* ctx);
+int gcs_keypoint_pyramid_ctx_set_stream(gcs_keypoint_pyramid_ctx* ctx, void* stream);
+/* Queues its kernels on the context's stream and returns; every output is a device array.  Refusals as
+ * gcs_detect_keypoints'. */
+int gcs_detect_keypoints_pyramid(gcs_keypoint_pyramid_ctx* ctx, const gcs_keypoint_inputs* in,
+                                 gcs_keypoint_pyramid_outputs* out);
+/* The same steps on the host (no device, no context): every pointer is a host array. */
+int gcs_detect_keypoints_pyramid_host(const gcs_keypoint_pyramid_config* cfg, const gcs_keypoint_inputs* in,
+                                      gcs_keypoint_pyramid_outputs* out);
+/* W_l, H_l, quota_l of every level for a width x height image, on the host; rows of levels >= n_levels are
+ * zero.  max_width and max_height do not bound width and height here. */
+int gcs_keypoint_pyramid_layout(const gcs_keypoint_pyramid_config* cfg, int32_t width, int32_t height,
+                                int32_t out[GCS_KEYPOINT_MAX_LEVELS][3]);
 
 /* ---------------------------------------------------------------- primitive path: map rendering */
 /* The reference's output side (backend/rendering.py, common/bev_pushforward.py) on the GPU, reading

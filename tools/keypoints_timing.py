@@ -10,9 +10,14 @@ each route after its own warm-up, the median of REPEAT calls:
   extract_detect    VisualFeatureExtractor.extract(depth, rgb, None, K): detector and feature operator chained
   extract_upload    the same keypoints passed as pageable numpy arrays: the only route before the detector
   extract_device    the same keypoints already on the device (the feature operator alone)
+  pyramid_queue     the pyramid detector's kernels alone (PyramidDetector.queue, the default PyramidConfig: 8 levels
+                    at 6 / 5); to be read against `queue`
+  pyramid_detect    PyramidDetector.detect: the kernels and the 144-byte read-back of counts and level_counts
+  extract_pyramid   VisualFeatureExtractor.extract(depth, rgb, None, K, keypoint_config=PyramidConfig()): pyramid
+                    detector and feature operator chained
 
---profile runs `detect` only, WARMUP + REPEAT times, for a kernel trace taken from outside.  Prints one JSON
-line."""
+--profile runs `detect` only and --profile-pyramid `pyramid_detect` only, WARMUP + REPEAT times, for a kernel trace
+taken from outside.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -38,6 +43,7 @@ def frame(np):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--profile-pyramid", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -49,6 +55,7 @@ def main():
     rgb_d, depth_d = torch.from_numpy(rgb).cuda(), torch.from_numpy(depth).cuda()
     K = PinholeIntrinsics(500.0, 500.0, 320.0, 240.0)
     det = KP.KeypointDetector()
+    pyr, pcfg = KP.PyramidDetector(), KP.PyramidConfig()
     ex = V.VisualFeatureExtractor(V.VisualFeatureConfig(response_soft_scale=1e-3))
     kp = det.detect(rgb_d)
     kp_host = tuple(k.cpu().numpy() for k in kp)
@@ -72,6 +79,12 @@ def main():
         print(json.dumps(dict(profile_calls=WARMUP + REPEAT)))
         return
 
+    if args.profile_pyramid:
+        for _ in range(WARMUP + REPEAT):
+            pyr.detect(rgb_d)
+        print(json.dumps(dict(profile_calls=WARMUP + REPEAT)))
+        return
+
     pinned = torch.empty(4, dtype=torch.int32).pin_memory()
     counts_d = torch.zeros(4, dtype=torch.int32, device="cuda")
 
@@ -81,16 +94,22 @@ def main():
         ev.record()
         ev.synchronize()
 
-    out = dict(width=W, height=H, warmup=WARMUP, repeat=REPEAT, counts=list(kp.counts))
+    pk = pyr.detect(rgb_d)
+    out = dict(width=W, height=H, warmup=WARMUP, repeat=REPEAT, counts=list(kp.counts), pyramid_counts=list(pk.counts),
+               pyramid_level_counts=[list(c) for c in pk.level_counts])
     for name, fn in (("detect", lambda: det.detect(rgb_d)),
                      ("queue", lambda: det.queue(rgb_d)),
                      ("readback", readback),
                      ("extract_detect", lambda: ex.extract(depth_d, rgb_d, None, K)),
                      ("extract_upload", lambda: ex.extract(depth_d, rgb_d, kp_host, K)),
-                     ("extract_device", lambda: ex.extract(depth_d, rgb_d, kp, K))):
+                     ("extract_device", lambda: ex.extract(depth_d, rgb_d, kp, K)),
+                     ("pyramid_queue", lambda: pyr.queue(rgb_d)),
+                     ("pyramid_detect", lambda: pyr.detect(rgb_d)),
+                     ("extract_pyramid", lambda: ex.extract(depth_d, rgb_d, None, K, keypoint_config=pcfg))):
         out[name + "_ms"], out[name + "_ms_p10_p90"] = timed(fn)
     print(json.dumps(out))
     det.close()
+    pyr.close()
     ex.close()
 
 
