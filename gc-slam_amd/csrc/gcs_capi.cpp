@@ -267,6 +267,10 @@ struct gcs_ctx {
   // one map for all hypotheses (GCS_MAP_*): the last scan's map-update record and the lead's record
   // carried by the last gcs_combine_allreduce
   int map_mode = GCS_MAP_OWN;
+  // gcs_scan_combine: the scan's tail leaves its pushforward (z_t, Sig6 in map_rec) to the combine, which
+  // submits it behind the all-reduce and k_payload_out (GCSLAM_PUSH_DEFER=0 / GCS_DEBUG_PUSH_DEFER 0: the
+  // tail submits it, as in the two-call API).  push_held: a deferred pushforward not yet submitted
+  bool push_defer = true, push_defer_now = false, push_held = false;
   double map_rec[GCS_MAP_REC_LEN] = {};
   double lead_rec[GCS_MAP_REC_LEN] = {};
   bool have_lead_rec = false;
@@ -956,6 +960,13 @@ int submit_push(gcs_ctx* c, const double* z_t, const double* Sig6, double gamma,
   return GCS_OK;
 }
 
+// gcs_scan_combine: the pushforward scan_tail held back (z_t and Sig6 are in map_rec), at most once
+int submit_held_push(gcs_ctx* c) {
+  if (!c || !c->push_held) return GCS_OK;
+  c->push_held = false;
+  return submit_push(c, c->map_rec + 6, c->map_rec + 12, c->cfg.forgetting_factor, c->push_stream, c->d_part_push);
+}
+
 // k_budget's launch call on the worker too (gcs_scan queues it before its host prologue): the main
 // thread goes straight to PredictDiffusion; stage_points waits for the worker (push_wait) before it
 // queues k_points behind it on the same stream, so the device order is the synchronous one.
@@ -1214,6 +1225,7 @@ int gcs_ctx_create(const gcs_config* cfg, gcs_ctx** out) {
   if (const char* g = getenv("GCSLAM_DEVICE_PREINT")) c->device_preint = atoi(g) != 0;
   if (const char* g = getenv("GCSLAM_DEVICE_IMU_ODOM")) c->device_imu_odom = atoi(g) != 0;
   if (const char* g = getenv("GCSLAM_PT_CLEAR")) c->pt_clear = atoi(g) != 0;
+  if (const char* g = getenv("GCSLAM_PUSH_DEFER")) c->push_defer = atoi(g) != 0;
   if (const char* g = getenv("GCSLAM_BEGIN_MIRROR")) c->begin_mirror = atoi(g) != 0;
   if (const char* g = getenv("GCSLAM_LIVE_ASYNC")) c->live_async = atoi(g) != 0;
   if (bad(hipHostMalloc(&c->h_preint_out, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent)))
@@ -1410,6 +1422,9 @@ int gcs_ctx_set_debug(gcs_ctx* c, int32_t key, int64_t value) {
     case GCS_DEBUG_COMBINE_DELAY:
       if (value < 0 || value > 1000000) return fail(c, GCS_ERR_ARG, "combine delay: 0..1000000 us");
       c->combine_delay_us = (int)value;
+      return GCS_OK;
+    case GCS_DEBUG_PUSH_DEFER:
+      c->push_defer = value != 0;
       return GCS_OK;
     case GCS_DEBUG_SENDBUF:
       if (value < -1 || value > 1) return fail(c, GCS_ERR_ARG, "send buffer: -1 (by world size), 0 host, 1 device");
@@ -2303,8 +2318,12 @@ int scan_tail(gcs_ctx* c, gcs_scan_state& st, const LidarTerms& lt, gcs_scan_out
   memcpy(c->map_rec + 6, z_t, 6 * sizeof(double));
   memcpy(c->map_rec + 12, Sig6, 36 * sizeof(double));
   auto Tq = clk::now();
-  if (push && c->map_mode != GCS_MAP_FOLLOW)  // a follower's map takes the lead's update (gcs_map_follow)
-    if (int rc = submit_push(c, z_t, Sig6, c->cfg.forgetting_factor, c->push_stream, c->d_part_push)) return rc;
+  if (push && c->map_mode != GCS_MAP_FOLLOW) {  // a follower's map takes the lead's update (gcs_map_follow)
+    if (c->push_defer_now)
+      c->push_held = true;  // gcs_scan_combine: submitted behind the combine's kernels (submit_held_push)
+    else if (int rc = submit_push(c, z_t, Sig6, c->cfg.forgetting_factor, c->push_stream, c->d_part_push))
+      return rc;
+  }
   auto Tr = clk::now();
   memcpy(out->z_t, z_t, sizeof(out->z_t));
   // 14 AnchorDriftUpdate (anchor_drift.py:93-191)
@@ -3010,9 +3029,24 @@ int gcs_combine_allreduce(gcs_ctx* c, void* comm, double w_iw, double w_bary, in
 int gcs_scan_combine(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_outputs* out, void* comm, double w_iw,
                      double w_bary, int32_t scan_count, gcs_belief* comb, double* cert, double* combine_ms) {
   const clk::time_point tc = clk::now();
-  if (int rc = gcs_scan(c, in, out)) return rc;
+  // The scan's pushforward (256 VGPRs, every CU for ~50 us at C3) is held back until the combine has
+  // queued its two small kernels: queued first, it took the slots their workgroups then waited for.
+  // It has the slack: the next scan's bin kernel joins it only after the combine, the next prologue
+  // and the point kernel.  Whatever the combine returns, a held pushforward is submitted exactly once.
+  if (c) {
+    c->push_held = false;
+    c->push_defer_now = c->push_defer;
+  }
+  const int rs = gcs_scan(c, in, out);
+  if (c) c->push_defer_now = false;
+  if (rs) {  // (the tail's last check, the belief's finiteness, comes after its pushforward)
+    (void)submit_held_push(c);
+    return rs;
+  }
   const clk::time_point t0 = clk::now();
-  const int rc = gcs_combine_allreduce(c, comm, w_iw, w_bary, scan_count, comb, cert);
+  int rc = gcs_combine_allreduce(c, comm, w_iw, w_bary, scan_count, comb, cert);
+  if (int rp = submit_held_push(c))  // an error path of the combine that left before its own submit
+    if (!rc) rc = rp;
   const clk::time_point t1 = clk::now();
   const double cm = ms_between(t0, t1);
   if (combine_ms) *combine_ms = cm;
@@ -3030,6 +3064,8 @@ int gcs_scan_combine(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_outputs* ou
 int gcs_combine_allreduce(gcs_ctx* c, void* comm, double w_iw, double w_bary, int32_t scan_count,
                           gcs_belief* comb, double* cert) {
   if (!c) return GCS_ERR_ARG;
+  if (!comm)  // host-only combine: nothing to queue ahead of gcs_scan_combine's held pushforward
+    if (int rc = submit_held_push(c)) return rc;
   constexpr int kLen = GCS_PAYLOAD_LEN + GCS_MAP_REC_LEN;
   if (!c->h_payload) {
     const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
@@ -3097,8 +3133,11 @@ int gcs_combine_allreduce(gcs_ctx* c, void* comm, double w_iw, double w_bary, in
     if (r != ncclSuccess) return fail(c, GCS_ERR_HIP, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
     HIPCHK(c, launch_payload_out(c->d_payload, c->dh_psum, len, c->d_pay_seq, s));
     const uint64_t seq = ++c->pay_seq;
+    // gcs_scan_combine's held pushforward goes out now: behind the two kernels above, ahead of the wait
+    const int rp = submit_held_push(c);
     if (int rc = wait_stamped(c, c->h_psum, len, seq, s, &c->pay_rereads, &c->pay_syncs, "hypothesis all-reduce"))
       return rc;
+    if (rp) return rp;
     sum = c->h_psum;
   }
   if (shared_map) {  // a single rank carries its own record (a follower then replays its own update)

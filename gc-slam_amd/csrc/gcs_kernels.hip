@@ -1305,9 +1305,15 @@ __device__ __forceinline__ double mass_scale_of(const double2* s_mw, double* m_i
 // DALL: phase D on every wave -- the first lane of each bin's lane group finalizes the bin from its
 // registers right after the lanes' xor tree (no LDS hand-off, no idle waves); required for tiles
 // wider than one wave (TB > 64).  !DALL: wave 0 alone, one lane per bin (the 64-bin tile's form).
-// No register target: the compiler's default allocation (for the small-stage instantiation -- C3,
-// 25 KiB of LDS, six workgroups per CU by LDS, register-bound -- 5 waves per SIMD needs <= 96 VGPRs
-// and the register allocator spills ~28 dwords to reach it).
+// No register target: the compiler's default allocation.  What it reports for gfx950 (the table of
+// tools/kernel_resources.py): 124-128 VGPRs and no scratch for every instantiation but <768, 128, 2>
+// (134), so four waves per SIMD = four 256-thread workgroups per CU by registers; by LDS, C3's
+// <320, 128, 2> (39,168 B) fits four per CU and C2's <512, 64, 4> (42,432 B) three.
+// As a persistent loop over tiles (min(tiles, resident workgroups) workgroups, a snake over the
+// dispatch positions, one barrier per tile) the same body measured slower and is not kept: the
+// compiler hoists the body's floating-point literals out of the tile loop (190-250 VGPRs; 114-145 only
+// with machine-level loop-invariant code motion off for the file), and then C3 ran 87.1-88.0 us against
+// 85.3-85.5 and C2, its tiles dealt out statically, 44.2 against 27.3.
 template <int STAGE, int TB, int LANES, bool DALL>
 __global__ __launch_bounds__(TB * LANES)
 void k_bins_scale(BinKernelArgs a, double* partials) {

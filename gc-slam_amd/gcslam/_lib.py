@@ -106,6 +106,7 @@ DEBUG_MIRROR_TORN = 9
 DEBUG_SENDBUF = 10
 DEBUG_DEVICE_IMU_ODOM = 11
 DEBUG_COMBINE_DELAY = 12
+DEBUG_PUSH_DEFER = 13
 MAP_OWN, MAP_LEAD, MAP_FOLLOW, MAP_REC_LEN = 0, 1, 2, 48
 
 

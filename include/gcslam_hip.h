@@ -259,6 +259,10 @@ int gcs_ctx_enable_timing(gcs_ctx* ctx, int32_t stage_mask);
  * straggling peer rank.  A delay past the host poll's 20 ms sends the wait to its stream-synchronize
  * path (gcs_ctx_mirror_stats' payload syncs count it); the combined state must not change.  Test knob. */
 #define GCS_DEBUG_COMBINE_DELAY 12
+/* GCS_DEBUG_PUSH_DEFER (default 1; GCSLAM_PUSH_DEFER=0 turns it off): gcs_scan_combine submits the scan's
+ * pushforward behind the combine's all-reduce and stage-out kernel instead of from the scan's tail; 0
+ * keeps the tail's submit (the two-call API's order; A/B knob and its bitwise test). */
+#define GCS_DEBUG_PUSH_DEFER 13
 int gcs_ctx_set_debug(gcs_ctx* ctx, int32_t key, int64_t value);
 /* The scan mirror (the PT fold's copy of the scan's scalars and device error words to pinned host
  * memory, with the scan's sequence number and a checksum; the host accepts it only when both match):
@@ -277,7 +281,9 @@ int gcs_ctx_stage_times(gcs_ctx* ctx, double* ms_sum /*GCS_N_STAGES*/, int64_t* 
 /* The host split of every gcs_scan since the last reset, summed (ms): [0..7] the scan's stage_ms
  * (gcs_scan_outputs: pre-device, device submit + wait, tail, whole scan, budget launch + predict,
  * device launch calls, tail numerics, pushforward launch calls), [8] gcs_scan_combine's combine, [9]
- * gcs_scan_combine's whole call; *n the scans counted (n_combine[0]: the combines).  Accumulated in the
+ * gcs_scan_combine's whole call (which submits the pushforward from its combine unless GCS_DEBUG_PUSH_DEFER
+ * is 0: its launch calls are then part of [8], not of [2] and [7]); *n the scans counted (n_combine[0]:
+ * the combines).  Accumulated in the
  * library on every scan, so a caller's timed region decomposes exactly, with no per-scan reads. */
 int gcs_ctx_host_split(gcs_ctx* ctx, double* ms_sum /*10*/, int64_t* n /*2*/, int32_t reset);
 /* The same split per scan, for its distribution (p50 / p90 / max, slow scans): the latest
