@@ -149,19 +149,20 @@ struct gcs_ctx {
   std::atomic<bool> push_stop{false}, push_sleeping{false};
   std::mutex push_mu;
   std::condition_variable push_cv;
+  enum JobKind {
+    JOB_PUSH,         // the scan's pushforward
+    JOB_BUDGET,       // the next scan's k_budget (row 1 mass sums)
+    JOB_LIVE_UPDATE,  // the live path's step 12b (gcs_live_scan): the new tiles' clears and the map update's launches
+  };
   struct PushJob {
-    // 0: the scan's pushforward, 1: the next scan's k_budget (row 1 mass sums), 2: the scan's device
-    // front (k_budget, the gated k_points, the push join, the bin kernel + fold, k_pt + fold, k_tile_order)
-    int kind;
-    const gcs_scan_inputs* in;
-    uint64_t seq;
-    double z_t[6], Sig6[36], gamma;
+    JobKind kind;
+    double z_t[6], Sig6[36], gamma;  // JOB_PUSH (z_t: JOB_LIVE_UPDATE too)
     hipStream_t s;
     double* partials;
     uint8_t* flags;
-    BudgetArgs ba;
+    BudgetArgs ba;  // JOB_BUDGET
     int nblk;
-    // 3: the live path's step 12b (gcs_live_scan): the new tiles' clears and the map update's launches
+    // JOB_LIVE_UPDATE
     gcs_pmap* pm;
     int32_t n12, ncl;
     int32_t tiles12[GCS_LIVE_MAX_TILES], clear12[GCS_LIVE_MAX_TILES];
@@ -171,27 +172,16 @@ struct gcs_ctx {
     gcs_pmap_update_config ucfg;
     gcs_pmap_update_inputs uin;
   };
-  // a ring of two job slots: a submission waits only while both are taken, so the next scan's front
+  // a ring of two job slots: a submission waits only while both are taken, so the next scan's k_budget
   // queues behind the last scan's pushforward launches instead of waiting for them
   PushJob push_jobs[2]{};
   int push_rc = 0;
   std::string push_err;
-  // launch gate of the pre-launched point stage (gcs_scan): [0] sequence word, [1..6] the deskew twist;
-  // coherent host memory polled by k_points (GCSLAM_GATE=0: the point stage is launched after the prologue)
-  uint64_t* h_gate = nullptr;
-  uint64_t* d_gate = nullptr;
-  double* d_gate_xi = nullptr;  // device memory: k_gate's copy of the twist for k_points
-  uint64_t gate_seq = 0, gate_next = 0;
-  // Measured and left off by default (GCSLAM_GATE=1 or GCS_DEBUG_LAUNCH_GATE turns it on): the
-  // worker is still making the last pushforward's launch calls when the front is queued, so k_points
-  // is launched no earlier than from the main thread, and the gate kernel adds a dependency hop:
-  // C2 113.5 vs 106.9 us per step, same box (profiles/r03/gate/)
-  bool gate_on = false;
-  bool gate_withhold = false;  // fault test (GCS_DEBUG_LAUNCH_GATE = -1): the gate is never opened
   // IMU weights + preintegration on the device (k_preint, GCSLAM_DEVICE_PREINT=1 or
-  // GCS_DEBUG_DEVICE_PREINT; not with the launch gate): the prologue stages the IMU window in pinned
-  // memory and queues k_preint, k_points reads its twist, the tail reads its record after the sync
+  // GCS_DEBUG_DEVICE_PREINT): the prologue stages the IMU window in pinned memory and queues k_preint,
+  // k_points reads its twist, the tail reads its record after the sync
   bool device_preint = false;
+  double* d_preint_xi = nullptr;  // device memory: the deskew twist k_preint writes and k_points reads (xi_dev)
   // the IMU / odometry evidence family on the device (k_imu_odom, gcs_imu_odom.hip; GCSLAM_DEVICE_IMU_ODOM=1
   // or GCS_DEBUG_DEVICE_IMU_ODOM): launched on io_stream by scan_imu_odom, its stamped record read by
   // finish_imu_odom before the tail needs the evidence
@@ -208,7 +198,7 @@ struct gcs_ctx {
   int64_t io_rereads = 0, io_syncs = 0;
   hipEvent_t ev_preint = nullptr;  // recorded after each k_preint: its window and record are not touched before it
   bool ev_preint_pending = false;
-  bool preint_pending = false;       // the next point stage reads the device twist (d_gate_xi)
+  bool preint_pending = false;       // the next point stage reads the device twist (d_preint_xi)
   bool preint_host_pending = false;  // st.xi / st.pre / cert[10] still to be read from h_preint_out
   double* h_preint_in = nullptr;     // pinned: the staged window (7 doubles per sample)
   int64_t preint_in_cap = 0;
@@ -222,10 +212,10 @@ struct gcs_ctx {
   uint64_t mirror_seq = 0;             // sequence number of the last mirror-writing PT fold
   int64_t mirror_scans = 0, mirror_rereads = 0, mirror_syncs = 0;  // accepted / re-read / via stream sync
   int mirror_torn = 0;                 // test knob (GCS_DEBUG_MIRROR_TORN): data stores delayed, in us
-  // device error words (BucketArgs.err, k_points' overflow, k_gate): [0] look-back bound exhausted,
-  // [1] degenerate-bucket compaction taken, [2] a direct bucket overflowed, [3] launch gate timeout.
-  // Device memory, carried to the host by the mirror (zeroed there) or by pull_err; h_err holds them
-  // until the host check that reads a word clears it.
+  // device error words (BucketArgs.err, k_points' overflow): [0] look-back bound exhausted,
+  // [1] degenerate-bucket compaction taken, [2] a direct bucket overflowed, [3] unused (the mirror
+  // packs the words in pairs, MIR_ERR).  Device memory, carried to the host by the mirror (zeroed
+  // there) or by pull_err; h_err holds them until the host check that reads a word clears it.
   uint32_t h_err[4] = {0u, 0u, 0u, 0u};
   uint32_t* d_err = nullptr;
   // direct buckets (gcs_scan, scale mode): k_points writes each bucket's members into a fixed row of
@@ -322,19 +312,16 @@ namespace {
 // Without a context (the push worker's calls) the message goes to this thread's slot, so the
 // worker reports the failing call's own error text rather than a later hipGetLastError().
 thread_local std::string t_fail_msg;
-// set on the push worker: its stage calls report into t_fail_msg (the main thread owns c->err), make
-// their launches themselves and do not wait for their own job
-thread_local bool t_on_worker = false;
 
 int fail(gcs_ctx* c, int code, const std::string& m) {
-  if (c && !t_on_worker) c->err = m;
+  if (c) c->err = m;
   else t_fail_msg = m;
   return code;
 }
 
-// wait until the push worker has made the launch calls of the last submitted pushforward
+// wait until the push worker has made the launch calls of every submitted job
 int push_wait(gcs_ctx* c) {
-  if (t_on_worker || !c->push_thread.joinable()) return GCS_OK;
+  if (!c->push_thread.joinable()) return GCS_OK;
   const uint64_t r = c->push_req.load(std::memory_order_acquire);
   while (c->push_done.load(std::memory_order_acquire) != r) __builtin_ia32_pause();
   if (c->push_rc) {
@@ -343,13 +330,6 @@ int push_wait(gcs_ctx* c) {
     return fail(c, rc, c->push_err);
   }
   return GCS_OK;
-}
-
-// a free job slot: waits while both are taken (the worker still launching two jobs)
-gcs_ctx::PushJob& claim_job(gcs_ctx* c) {
-  const uint64_t r = c->push_req.load(std::memory_order_relaxed);
-  while (r - c->push_done.load(std::memory_order_acquire) >= 2) __builtin_ia32_pause();
-  return c->push_jobs[r & 1];
 }
 
 // order the main stream after an in-flight scan pushforward (map, derived, touched, map totals)
@@ -501,13 +481,19 @@ int upload_atlas(gcs_ctx* c) {
 
 int submit_budget(gcs_ctx* c, const BudgetArgs& ba, int nblk, hipStream_t s);
 
+// Self-budget eligibility of a scale-mode call that goes on to the bin kernel (gcs_scan, its sorted
+// redo, gcs_map_follow): the bin kernel folds the mass rows a self-budget point stage leaves.  Every
+// other point stage (gcs_scan_begin's deskew, the per-operator entry point) takes a real k_budget.
+bool bin_path_self(const gcs_ctx* c) { return c->self_budget && c->cfg.mode == GCS_MODE_SCALE; }
+
 // ---------------------------------------------------------------- device stages
 // fold_later: leave k_points' cert fold to block 0 of the next k_bins_scale (scale-mode scan)
 // Row 1's mass sums (k_budget) need only the weights: gcs_scan queues them before its host
 // prologue so they run while the host predicts and preintegrates.  Timed (stage ST_BUDGET), the launch
 // is made here with the kernel's own start / end events; otherwise by the worker thread.
-// self: a self-budget scan (gcs_ctx::self_budget): only the per-scan clears are launched, when the last
-// scan's k_pt did not do them (k_budget with no weights to sum); usually nothing is.
+// self: a self-budget scan (bin_path_self): only the per-scan clears are launched, when the last
+// scan's k_pt did not do them (k_budget with no weights to sum); usually nothing is.  The caller
+// decides it, because only the caller knows that the bin kernel follows the point stage.
 int stage_budget(gcs_ctx* c, const double* w, int n_raw, bool toggle = true, bool self = false) {
   if (n_raw < 0 || n_raw > c->max_raw) return fail(c, GCS_ERR_ARG, "n_points exceeds max_raw_points");
   int stride = std::max(1, (int)((n_raw + (long)c->cap - 1) / c->cap));  // ceil(N/cap), point_budget.py:160
@@ -545,7 +531,7 @@ int stage_budget(gcs_ctx* c, const double* w, int n_raw, bool toggle = true, boo
     ba.n_raw = 0;  // the clears only (its zero partial rows are read by nobody)
   }
   StageEv ev = stage_ev(c, ST_BUDGET);
-  if (!ev.e0 && c->push_async && !t_on_worker) return submit_budget(c, ba, c->budget_blocks, s);
+  if (!ev.e0 && c->push_async) return submit_budget(c, ba, c->budget_blocks, s);
   if (int rc = push_wait(c)) return rc;  // the worker's queued launches precede this one on the stream
   HIPCHK(c, launch_budget(ba, c->budget_blocks, s, ev.e0, ev.e1));
   return GCS_OK;
@@ -560,12 +546,12 @@ int stage_points(gcs_ctx* c, const void* xyz, int point_step, const double* t, c
   if (n_raw < 0 || n_raw > c->max_raw) return fail(c, GCS_ERR_ARG, "n_points exceeds max_raw_points");
   if (point_step < (xyz_f64 ? 24 : 12)) return fail(c, GCS_ERR_ARG, "point_step too small for x, y, z");
   StageEv ev = stage_ev(c, ST_POINTS);
-  // a self-budget scan: scale mode, the cert fold left to the bin kernel, no per-point outputs (they
-  // carry the budget weights) -- gcs_scan, its pre-launched front and gcs_map_follow
-  const bool self_ok = c->self_budget && c->cfg.mode == GCS_MODE_SCALE && !deskew_only && fold_later && !p0_out &&
-                       !w_out && !wb_out && !iz_out && !t_out;
-  if (!c->budget_pending)  // k_budget not queued earlier by gcs_scan
-    if (int rc = stage_budget(c, w, n_raw, true, self_ok)) return rc;
+  if (!c->budget_pending)  // not queued by the caller (the per-operator entry point): a real k_budget
+    if (int rc = stage_budget(c, w, n_raw)) return rc;
+  // the guard of the callers' choice (bin_path_self): a self-budget point stage is a scale-mode one with
+  // the cert fold left to the bin kernel and no per-point outputs (they carry the budget weights)
+  const bool self_ok = c->cfg.mode == GCS_MODE_SCALE && !deskew_only && fold_later && !p0_out && !w_out && !wb_out &&
+                       !iz_out && !t_out;
   if (c->budget_self && !self_ok) return fail(c, GCS_ERR_STATE, "self-budget point stage with per-point outputs");
   if (int rc = push_wait(c)) return rc;  // k_budget's launch call (worker) precedes k_points on the stream
   c->budget_pending = false;
@@ -617,12 +603,8 @@ int stage_points(gcs_ctx* c, const void* xyz, int point_step, const double* t, c
   a.nearest_out = c->d_nearest;  // device ids
   a.iz_out = iz_out;
   a.t_out = t_out;
-  if (c->gate_next) {  // pre-launched by the scan front: k_gate waits for the twist, k_points reads it
-    HIPCHK(c, launch_gate(c->d_gate, c->gate_next, c->d_gate_xi, c->d_err + 3, s));
-    a.xi_dev = c->d_gate_xi;
-    c->gate_next = 0;
-  } else if (c->preint_pending) {  // k_preint, queued by the prologue on this stream, wrote the twist
-    a.xi_dev = c->d_gate_xi;
+  if (c->preint_pending) {  // k_preint, queued by the prologue on this stream, wrote the twist
+    a.xi_dev = c->d_preint_xi;
     c->preint_pending = false;
   }
   c->iz_valid = false;
@@ -878,12 +860,9 @@ int stage_push(gcs_ctx* c, const double* z_t, const double* Sig6, double gamma, 
 
 // The push worker: waits (spin, then sleep) for a submitted job and makes its launch calls with the
 // job's captured arguments (the flags buffer of that scan; the context's device buffers are fixed).
-int scan_front(gcs_ctx* c, const gcs_scan_inputs* in, uint64_t seq);
-
 void push_worker(gcs_ctx* c) {
   (void)hipSetDevice(c->cfg.device);
   c->worker_tid.store((int64_t)syscall(SYS_gettid));
-  t_on_worker = true;
   uint64_t seen = 0;
   for (;;) {
     // spin for up to 2 ms after the last job (a scan every 0.1-0.3 ms keeps the worker awake: a
@@ -907,22 +886,19 @@ void push_worker(gcs_ctx* c) {
       const gcs_ctx::PushJob& j = c->push_jobs[seen & 1];
       int rc = GCS_OK;
       std::string msg;
-      if (j.kind == 1) {
+      if (j.kind == gcs_ctx::JOB_BUDGET) {
         const hipError_t e = launch_budget(j.ba, j.nblk, j.s, nullptr, nullptr);
         if (e != hipSuccess) {
           rc = GCS_ERR_HIP;
           msg = "k_budget launch (worker): " + std::string(hipGetErrorString(e));
         }
-      } else if (j.kind == 2) {
-        rc = scan_front(c, j.in, j.seq);
-        if (rc) msg = "scan front launch (worker): " + t_fail_msg;
-      } else if (j.kind == 3) {
+      } else if (j.kind == gcs_ctx::JOB_LIVE_UPDATE) {
         for (int k = 0; k < j.ncl && !rc; ++k) rc = live::pmap_clear_tile_launch(j.pm, j.clear12[k]);
         if (!rc)
           rc = live::pmap_update_launch(j.pm, j.tiles12, j.tids12, j.n12, j.z_t, j.ts12, j.seq12, j.next12, &j.ucfg,
                                         &j.uin);
         if (rc) msg = "gcs_pmap_map_update (live path, worker): " + std::string(gcs_pmap_last_error(j.pm));
-      } else {
+      } else {  // JOB_PUSH
         rc = stage_push(c, j.z_t, j.Sig6, j.gamma, j.s, j.partials, j.flags, true);
         if (rc) msg = "pushforward launch (worker): " + t_fail_msg;
       }
@@ -935,6 +911,24 @@ void push_worker(gcs_ctx* c) {
   }
 }
 
+// Post a job to the push worker (started on first use): claims a free slot of the ring -- waiting
+// while both are taken, the worker still launching two jobs -- lets fill write it, publishes it and
+// wakes the worker if it sleeps.
+template <class Fill>
+void post_job(gcs_ctx* c, gcs_ctx::JobKind kind, Fill&& fill) {
+  if (!c->push_thread.joinable()) c->push_thread = std::thread(push_worker, c);
+  const uint64_t r = c->push_req.load(std::memory_order_relaxed);
+  while (r - c->push_done.load(std::memory_order_acquire) >= 2) __builtin_ia32_pause();
+  gcs_ctx::PushJob& j = c->push_jobs[r & 1];
+  j.kind = kind;
+  fill(j);
+  c->push_req.fetch_add(1);
+  if (c->push_sleeping.load()) {
+    std::lock_guard<std::mutex> lk(c->push_mu);
+    c->push_cv.notify_one();
+  }
+}
+
 // launch the scan's pushforward: on the worker (default) or inline (timing the push stage, or
 // GCSLAM_PUSH_THREAD=0)
 int submit_push(gcs_ctx* c, const double* z_t, const double* Sig6, double gamma, hipStream_t s, double* partials) {
@@ -943,20 +937,14 @@ int submit_push(gcs_ctx* c, const double* z_t, const double* Sig6, double gamma,
     if (int rc = push_wait(c)) return rc;
     return stage_push(c, z_t, Sig6, gamma, s, partials, c->d_flags);
   }
-  if (!c->push_thread.joinable()) c->push_thread = std::thread(push_worker, c);
-  gcs_ctx::PushJob& j = claim_job(c);
-  j.kind = 0;
-  memcpy(j.z_t, z_t, sizeof(j.z_t));
-  memcpy(j.Sig6, Sig6, sizeof(j.Sig6));
-  j.gamma = gamma;
-  j.s = s;
-  j.partials = partials;
-  j.flags = c->d_flags;
-  c->push_req.fetch_add(1);
-  if (c->push_sleeping.load()) {
-    std::lock_guard<std::mutex> lk(c->push_mu);
-    c->push_cv.notify_one();
-  }
+  post_job(c, gcs_ctx::JOB_PUSH, [&](gcs_ctx::PushJob& j) {
+    memcpy(j.z_t, z_t, sizeof(j.z_t));
+    memcpy(j.Sig6, Sig6, sizeof(j.Sig6));
+    j.gamma = gamma;
+    j.s = s;
+    j.partials = partials;
+    j.flags = c->d_flags;
+  });
   return GCS_OK;
 }
 
@@ -971,79 +959,13 @@ int submit_held_push(gcs_ctx* c) {
 // thread goes straight to PredictDiffusion; stage_points waits for the worker (push_wait) before it
 // queues k_points behind it on the same stream, so the device order is the synchronous one.
 int submit_budget(gcs_ctx* c, const BudgetArgs& ba, int nblk, hipStream_t s) {
-  if (!c->push_thread.joinable()) c->push_thread = std::thread(push_worker, c);
-  gcs_ctx::PushJob& j = claim_job(c);  // (queued behind the last scan's pushforward launches)
-  j.kind = 1;
-  j.ba = ba;
-  j.nblk = nblk;
-  j.s = s;
-  c->push_req.fetch_add(1);
-  if (c->push_sleeping.load()) {
-    std::lock_guard<std::mutex> lk(c->push_mu);
-    c->push_cv.notify_one();
-  }
+  post_job(c, gcs_ctx::JOB_BUDGET, [&](gcs_ctx::PushJob& j) {  // (queued behind the last scan's pushforward launches)
+    j.ba = ba;
+    j.nblk = nblk;
+    j.s = s;
+  });
   return GCS_OK;
 }
-
-// The scan's device front, queued by the worker while the main thread runs the host prologue:
-// k_budget, k_points behind the launch gate (it waits on the device for the twist), the join with
-// the last pushforward, the bin kernel + fold, k_pt + fold (mirror, ready word) and k_tile_order --
-// the launch calls and the dispatch latency of the point stage leave the scan's critical path.
-int scan_front(gcs_ctx* c, const gcs_scan_inputs* in, uint64_t seq) {
-  static const double kNoTwist[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  c->budget_pending = false;
-  c->gate_next = seq;
-  if (int rc = stage_points(c, in->xyz_dev, in->point_step, in->timestamps_dev, in->weights_dev, in->n_points,
-                            in->scan_start_time, in->scan_end_time, kNoTwist, nullptr, nullptr, nullptr,
-                            /*fold_later=*/true, in->xyz_format == 1))
-    return rc;
-  if (int rc = join_push(c)) return rc;
-  if (int rc = stage_bins(c)) return rc;
-  if (int rc = stage_pt(c, /*to_host=*/true, /*clear_next=*/true)) return rc;
-  return stage_tile_order(c);
-}
-
-int submit_front(gcs_ctx* c, const gcs_scan_inputs* in, uint64_t seq) {
-  if (!c->push_thread.joinable()) c->push_thread = std::thread(push_worker, c);
-  gcs_ctx::PushJob& j = claim_job(c);  // (queued behind the last scan's pushforward launches)
-  j.kind = 2;
-  j.in = in;
-  j.seq = seq;
-  c->push_req.fetch_add(1);
-  if (c->push_sleeping.load()) {
-    std::lock_guard<std::mutex> lk(c->push_mu);
-    c->push_cv.notify_one();
-  }
-  return GCS_OK;
-}
-
-// the twist, then the sequence word (x86 stores are ordered; the fence keeps the compiler's order)
-void open_gate(gcs_ctx* c, const double* xi) {
-  volatile uint64_t* g = c->h_gate;
-  for (int k = 0; k < 6; ++k) {
-    uint64_t u;
-    memcpy(&u, xi + k, sizeof(u));
-    g[1 + k] = u;
-  }
-  std::atomic_thread_fence(std::memory_order_release);
-  __atomic_store_n(c->h_gate, c->gate_seq, __ATOMIC_RELEASE);
-}
-
-// On every early return of a pre-launched scan: opens the gate (zero twist), so no point block waits
-// for its timeout, and waits for the worker's launch calls, which read the context's per-scan state
-struct GateGuard {
-  gcs_ctx* c;
-  bool open = false, joined = false;
-  ~GateGuard() {
-    static const double kNoTwist[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (!open && !c->gate_withhold) open_gate(c, kNoTwist);
-    if (!joined) {
-      const std::string keep = c->err;  // the scan's own failure is the message to report
-      (void)push_wait(c);
-      c->err = keep;
-    }
-  }
-};
 
 // after a stream sync: a k_scan whose look-back bound ran out left wrong bucket starts
 int check_bucket_err(gcs_ctx* c) {
@@ -1216,12 +1138,7 @@ int gcs_ctx_create(const gcs_config* cfg, gcs_ctx** out) {
   if (bad(hipHostGetDevicePointer((void**)&c->d_scalars_mirror, c->h_scalars, 0))) return GCS_ERR_HIP;
   if (bad(hipMalloc(&c->d_err, 4 * sizeof(uint32_t)))) return GCS_ERR_HIP;
   if (bad(hipMemset(c->d_err, 0, 4 * sizeof(uint32_t)))) return GCS_ERR_HIP;
-  if (bad(hipHostMalloc(&c->h_gate, 8 * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent)))
-    return GCS_ERR_HIP;
-  for (int k = 0; k < 8; ++k) c->h_gate[k] = 0u;
-  if (bad(hipHostGetDevicePointer((void**)&c->d_gate, c->h_gate, 0))) return GCS_ERR_HIP;
-  if (bad(hipMalloc(&c->d_gate_xi, 8 * sizeof(double)))) return GCS_ERR_HIP;
-  if (const char* g = getenv("GCSLAM_GATE")) c->gate_on = atoi(g) != 0;
+  if (bad(hipMalloc(&c->d_preint_xi, 8 * sizeof(double)))) return GCS_ERR_HIP;
   if (const char* g = getenv("GCSLAM_DEVICE_PREINT")) c->device_preint = atoi(g) != 0;
   if (const char* g = getenv("GCSLAM_DEVICE_IMU_ODOM")) c->device_imu_odom = atoi(g) != 0;
   if (const char* g = getenv("GCSLAM_PT_CLEAR")) c->pt_clear = atoi(g) != 0;
@@ -1318,7 +1235,7 @@ int gcs_ctx_destroy(gcs_ctx* c) {
   }
   if (c->push_stream) (void)hipStreamSynchronize(c->push_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  void* ptrs[] = {c->d_gate_xi, c->d_members, c->d_bin_dirs, c->d_knn, c->d_rknn_off, c->d_rknn, c->d_pools, c->d_pool_bound, c->d_recs, c->d_iz, c->d_live_p0, c->d_live_w, c->d_live_t, c->d_keys, c->d_slots,
+  void* ptrs[] = {c->d_preint_xi, c->d_members, c->d_bin_dirs, c->d_knn, c->d_rknn_off, c->d_rknn, c->d_pools, c->d_pool_bound, c->d_recs, c->d_iz, c->d_live_p0, c->d_live_w, c->d_live_t, c->d_keys, c->d_slots,
                   c->d_sorted, c->d_nearest, c->d_counts, c->d_starts, c->d_perm, c->d_flags_buf[0], c->d_touched,
                   c->d_tile_dirty, c->d_tile_order, c->d_tile_work, c->d_bins_part, c->d_tickets,
                   c->d_bin_ref, c->d_tile_src_off, c->d_tile_src, c->d_rknn_local, c->d_part_pts, c->d_mass_rows, c->d_part_push, c->d_parse_flag,
@@ -1327,7 +1244,6 @@ int gcs_ctx_destroy(gcs_ctx* c) {
     if (p) (void)hipFree(p);
   if (c->h_scalars) (void)hipHostFree(c->h_scalars);
   if (c->d_err) (void)hipFree(c->d_err);
-  if (c->h_gate) (void)hipHostFree(c->h_gate);
   if (c->h_preint_in) (void)hipHostFree(c->h_preint_in);
   if (c->h_preint_out) (void)hipHostFree(c->h_preint_out);
   if (c->comm_stream) {
@@ -1409,11 +1325,6 @@ int gcs_ctx_set_debug(gcs_ctx* c, int32_t key, int64_t value) {
       return GCS_OK;
     case GCS_DEBUG_PT_CLEAR:
       c->pt_clear = value != 0;
-      return GCS_OK;
-    case GCS_DEBUG_LAUNCH_GATE:
-      if (value < -1 || value > 1) return fail(c, GCS_ERR_ARG, "launch gate: -1, 0 or 1");
-      c->gate_on = value != 0;
-      c->gate_withhold = value < 0;
       return GCS_OK;
     case GCS_DEBUG_MIRROR_TORN:
       if (value < 0 || value > 10000) return fail(c, GCS_ERR_ARG, "mirror torn delay: 0..10000 us");
@@ -1524,7 +1435,7 @@ int gcs_ctx_enable_timing(gcs_ctx* c, int32_t stage_mask) {
 
 int gcs_ctx_stage_times(gcs_ctx* c, double* ms_sum, int64_t* counts, int32_t reset) {
   if (!c) return GCS_ERR_ARG;
-  if (int rc = push_wait(c)) return rc;  // the worker queues stage events of the scan front
+  if (int rc = push_wait(c)) return rc;  // the worker's queued launch calls first
   harvest(c);
   for (int st = 0; st < kStages; ++st) {
     if (ms_sum) ms_sum[st] = c->stage_ms_sum[st];
@@ -1871,7 +1782,7 @@ int launch_device_preint(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_state& 
     a.g[k] = c->grav[k];
   }
   a.rotation_only = c->cfg.deskew_rotation_only ? 1 : 0;
-  a.xi_dev = c->d_gate_xi;
+  a.xi_dev = c->d_preint_xi;
   a.host_out = c->h_preint_out;
   HIPCHK(c, launch_preint(a, c->stream));
   if (!c->ev_preint) HIPCHK(c, hipEventCreateWithFlags(&c->ev_preint, hipEventDisableTiming));
@@ -1900,15 +1811,12 @@ void finish_preint(gcs_ctx* c, gcs_scan_state& st) {
   st.cert[10] = st.pre.ess;
 }
 
-int scan_prologue(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_state& st, bool budget = true) {
+// self: the caller's point stage is a self-budget one (bin_path_self; stage_budget)
+int scan_prologue(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_state& st, bool self) {
   st.T0 = clk::now();
   c->preint_pending = c->preint_host_pending = false;  // (a failed scan may have left them set)
-  if (budget) {  // (the pre-launched front queues k_budget itself)
-    c->budget_pending = false;
-    if (int rc0 = stage_budget(c, in->weights_dev, in->n_points, true,
-                               c->self_budget && c->cfg.mode == GCS_MODE_SCALE))  // runs during the prologue
-      return rc0;
-  }
+  c->budget_pending = false;
+  if (int rc0 = stage_budget(c, in->weights_dev, in->n_points, true, self)) return rc0;  // runs during the prologue
   const double* Q = in->Q ? in->Q : c->Q;
   double* cert = st.cert;
   memset(cert, 0, sizeof(st.cert));
@@ -1933,7 +1841,7 @@ int scan_prologue(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_state& st, boo
   cert[38] = st.sigma_warp;
   host::spd_factor_solve(fpred, st.pred.h, st.mu_inc);
   host::world_pose_from_increment(st.prev, st.mu_prev, st.pose0);
-  if (budget && c->device_preint) {  // k_preint on the stream ahead of the point stage
+  if (c->device_preint) {  // k_preint on the stream ahead of the point stage
     if (int rc = launch_device_preint(c, in, st)) return rc;
     st.T1 = clk::now();
     return GCS_OK;
@@ -2371,6 +2279,32 @@ int scan_tail(gcs_ctx* c, gcs_scan_state& st, const LidarTerms& lt, gcs_scan_out
   return GCS_OK;
 }
 
+// Direct buckets for one call's stages (scale mode, unless a bucket overflowed before); off again when
+// the call returns: the per-operator entry points always take the sorted path.
+struct DirectScope {
+  gcs_ctx* c;
+  explicit DirectScope(gcs_ctx* c_) : c(c_) {
+    c->use_direct = c->cfg.mode == GCS_MODE_SCALE && c->direct_buckets && !c->sorted_sticky && c->d_members;
+  }
+  ~DirectScope() { c->use_direct = false; }
+};
+
+// gcs_scan's device stages behind the queued budget, for the first attempt and for the sorted redo:
+// 1,3,4-6 budget gather, deskew, soft assign, moment match; 7,8 the MF + planar reductions; the PT
+// fold's mirror for wait_mirror.  (In the redo the join finds no pushforward pending.)
+int scan_stages(gcs_ctx* c, const gcs_scan_inputs* in, const double* xi) {
+  if (int rc = stage_points(c, in->xyz_dev, in->point_step, in->timestamps_dev, in->weights_dev, in->n_points,
+                            in->scan_start_time, in->scan_end_time, xi, nullptr, nullptr, nullptr, /*fold_later=*/true,
+                            in->xyz_format == 1))
+    return rc;
+  if (int rc = join_push(c)) return rc;   // the bin kernel reads the map the previous scan's pushforward wrote
+  if (int rc = stage_bins(c)) return rc;  // scale mode: Matrix-Fisher reduction + R_mf fused in
+  if (c->cfg.mode != GCS_MODE_SCALE)
+    if (int rc = stage_mf(c)) return rc;
+  if (int rc = stage_pt(c, /*to_host=*/true, /*clear_next=*/true)) return rc;
+  return stage_tile_order(c);
+}
+
 }  // namespace
 
 int gcs_scan(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_outputs* out) {
@@ -2379,51 +2313,16 @@ int gcs_scan(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_outputs* out) {
   c->live_pending = false;
   // this scan's device error words arrive with its own mirror: none of an earlier, failed call's stays
   memset(c->h_err, 0, sizeof(c->h_err));
-  // direct buckets for this call's stages (scale mode, unless a bucket overflowed before)
-  c->use_direct = c->cfg.mode == GCS_MODE_SCALE && c->direct_buckets && !c->sorted_sticky && c->d_members;
-  struct DirectOff {
-    gcs_ctx* c;
-    ~DirectOff() { c->use_direct = false; }  // per-operator entry points always take the sorted path
-  } direct_off{c};
+  DirectScope direct(c);
   gcs_scan_state& st = *c->scan_st;
+  const bool self = bin_path_self(c);  // the bin kernel follows the point stage, here and in the redo
   int rc = 0;
-  // pre-launched front (direct buckets, worker thread, budget / point stages not event-timed): the
-  // device stages are queued now and the point kernel waits on the device for the prologue's twist
-  const uint32_t front_timed = (1u << ST_BUDGET) | (1u << ST_POINTS);
-  if (c->gate_on && c->push_async && c->use_direct && c->h_gate && !(c->timing_mask & front_timed)) {
-    GateGuard guard{c};
-    ++c->gate_seq;
-    st.T0 = clk::now();
-    if ((rc = submit_front(c, in, c->gate_seq))) return rc;
-    if ((rc = scan_prologue(c, in, st, /*budget=*/false))) return rc;
-    if (!c->gate_withhold) open_gate(c, st.xi);
-    guard.open = true;
-    st.Ts = clk::now();
-    if ((rc = scan_imu_odom(c, in, st, out))) return rc;
-    guard.joined = true;
-    if ((rc = push_wait(c))) return rc;  // the front's launch calls (and their errors)
-    if ((rc = wait_mirror(c))) return rc;
-    if (c->h_err[3]) {
-      c->h_err[3] = 0u;
-      return fail(c, GCS_ERR_HIP, "k_points: launch gate not opened within its timeout");
-    }
-  } else {
-    if ((rc = scan_prologue(c, in, st))) return rc;
-    // 1,3,4-6 device: budget, deskew, soft assign, moment match; 7,8 MF + planar reductions
-    rc = stage_points(c, in->xyz_dev, in->point_step, in->timestamps_dev, in->weights_dev, in->n_points,
-                      in->scan_start_time, in->scan_end_time, st.xi, nullptr, nullptr, nullptr, /*fold_later=*/true,
-                      in->xyz_format == 1);
-    if (rc) return rc;
-    if (int rc_ = join_push(c)) return rc_;  // the bin kernel reads the map the previous scan's pushforward wrote
-    if ((rc = stage_bins(c))) return rc;  // scale mode: Matrix-Fisher reduction + R_mf fused in
-    if (c->cfg.mode != GCS_MODE_SCALE && (rc = stage_mf(c))) return rc;
-    if ((rc = stage_pt(c, /*to_host=*/true, /*clear_next=*/true))) return rc;
-    if ((rc = stage_tile_order(c))) return rc;
-    st.Ts = clk::now();
-    if ((rc = scan_imu_odom(c, in, st, out))) return rc;
-    if ((rc = wait_mirror(c))) return rc;  // the PT fold has written the scalars to h_scalars
-    finish_preint(c, st);
-  }
+  if ((rc = scan_prologue(c, in, st, self))) return rc;
+  if ((rc = scan_stages(c, in, st.xi))) return rc;
+  st.Ts = clk::now();
+  if ((rc = scan_imu_odom(c, in, st, out))) return rc;
+  if ((rc = wait_mirror(c))) return rc;  // the PT fold has written the scalars to h_scalars
+  finish_preint(c, st);
   if ((rc = check_bucket_err(c))) return rc;
   bool redone = false;
   if (c->use_direct && c->h_err[2]) {
@@ -2433,16 +2332,8 @@ int gcs_scan(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_outputs* out) {
     c->sorted_sticky = true;
     c->use_direct = false;
     redone = true;
-    if ((rc = stage_budget(c, in->weights_dev, in->n_points, /*toggle=*/false,
-                           c->self_budget && c->cfg.mode == GCS_MODE_SCALE)))
-      return rc;
-    if ((rc = stage_points(c, in->xyz_dev, in->point_step, in->timestamps_dev, in->weights_dev, in->n_points,
-                           in->scan_start_time, in->scan_end_time, st.xi, nullptr, nullptr, nullptr, true,
-                           in->xyz_format == 1)))
-      return rc;
-    if ((rc = stage_bins(c))) return rc;
-    if ((rc = stage_pt(c, /*to_host=*/true, /*clear_next=*/true))) return rc;
-    if ((rc = stage_tile_order(c))) return rc;
+    if ((rc = stage_budget(c, in->weights_dev, in->n_points, /*toggle=*/false, self))) return rc;
+    if ((rc = scan_stages(c, in, st.xi))) return rc;
     if ((rc = wait_mirror(c))) return rc;
     if ((rc = check_bucket_err(c))) return rc;
   }
@@ -2464,8 +2355,14 @@ int gcs_scan_begin(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_outputs
   // this scan's device error words arrive with its own mirror: none of an earlier, failed call's stays
   memset(c->h_err, 0, sizeof(c->h_err));
   c->use_direct = false;
+  // Scale mode, after a gcs_scan: this call's k_budget takes the other flag buffer, so the next
+  // gcs_scan's k_budget clears the buffer that scan's pushforward reads.  The main stream is ordered
+  // behind that pushforward first (as the per-operator point stage does).
+  if (int rc = join_push(c)) return rc;
   gcs_scan_state& st = *c->scan_st;
-  if (int rc = scan_prologue(c, in, st)) return rc;
+  // a real k_budget in either mode: the deskew-only point stage gathers with its mass sums and writes
+  // per-point outputs, and no bin kernel follows to fold a self-budget stage's mass rows
+  if (int rc = scan_prologue(c, in, st, /*self=*/false)) return rc;
   // 1 + 3 on the device: budget gather, deskew, window weights (no soft assign, no bins)
   double* p0 = out->points_dev ? out->points_dev : c->d_live_p0;
   double* tt = out->timestamps_dev ? out->timestamps_dev : c->d_live_t;
@@ -2780,49 +2677,6 @@ int gcs_live_scan_camera(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_o
   if ((rc = gcs_scan_finish(c, &ev, out))) return rc;
   mark(5);
   // step 12b at z_t over the active tiles (:1232-1492); new tiles on written slots start cleared
-  if (c->live_async && c->push_async) {  // the launch calls on the worker: the caller builds its results meanwhile
-    if (!c->push_thread.joinable()) c->push_thread = std::thread(push_worker, c);
-    gcs_ctx::PushJob& j = claim_job(c);
-    j.kind = 3;
-    j.pm = pm;
-    j.n12 = na;
-    j.ncl = ncl;
-    memcpy(j.tiles12, lo->active_slots, sizeof(int32_t) * na);
-    memcpy(j.tids12, lo->active_ids, sizeof(int64_t) * na);
-    memcpy(j.clear12, clear, sizeof(int32_t) * ncl);
-    memcpy(j.z_t, out->z_t, sizeof(j.z_t));
-    j.ts12 = a->timestamp;
-    j.seq12 = a->scan_seq;
-    j.next12 = a->next_global_id;
-    j.ucfg = *a->update_cfg;
-    gcs_pmap_update_inputs& ui = j.uin;
-    ui = gcs_pmap_update_inputs{};
-    ui.Lambdas = m.Lambdas;
-    ui.thetas = m.thetas;
-    ui.etas = m.etas;
-    ui.weights = m.weights;
-    ui.valid = m.valid_mask;
-    ui.colors = a->batch_colors;
-    ui.sources = a->batch_sources;
-    ui.n_total = m.n_total;
-    ui.n_lobes = m.n_lobes;
-    ui.responsibilities = ao->responsibilities;
-    ui.candidate_tile_ids = ao->candidate_tile_ids;
-    ui.candidate_slots = ao->candidate_slots;
-    ui.row_masses = ao->row_masses;
-    ui.k_assoc = a->assoc_cfg->k_assoc;
-    c->push_req.fetch_add(1);
-    if (c->push_sleeping.load()) {
-      std::lock_guard<std::mutex> lk(c->push_mu);
-      c->push_cv.notify_one();
-    }
-    lo->next_global_id = a->next_global_id;
-    c->live_map = pm;
-    mark(6);
-    return GCS_OK;
-  }
-  for (int k = 0; k < ncl; ++k)
-    if ((rc = live::pmap_clear_tile_launch(pm, clear[k]))) return sub_fail(c, rc, "gcs_pmap_clear_tile", gcs_pmap_last_error(pm));
   gcs_pmap_update_inputs ui{};
   ui.Lambdas = m.Lambdas;
   ui.thetas = m.thetas;
@@ -2838,9 +2692,28 @@ int gcs_live_scan_camera(gcs_ctx* c, const gcs_scan_inputs* in, gcs_scan_begin_o
   ui.candidate_slots = ao->candidate_slots;
   ui.row_masses = ao->row_masses;
   ui.k_assoc = a->assoc_cfg->k_assoc;
-  if ((rc = live::pmap_update_launch(pm, lo->active_slots, lo->active_ids, na, out->z_t, a->timestamp, a->scan_seq,
-                                     a->next_global_id, a->update_cfg, &ui)))
-    return sub_fail(c, rc, "gcs_pmap_map_update", gcs_pmap_last_error(pm));
+  if (c->live_async && c->push_async) {  // the launch calls on the worker: the caller builds its results meanwhile
+    post_job(c, gcs_ctx::JOB_LIVE_UPDATE, [&](gcs_ctx::PushJob& j) {
+      j.pm = pm;
+      j.n12 = na;
+      j.ncl = ncl;
+      memcpy(j.tiles12, lo->active_slots, sizeof(int32_t) * na);
+      memcpy(j.tids12, lo->active_ids, sizeof(int64_t) * na);
+      memcpy(j.clear12, clear, sizeof(int32_t) * ncl);
+      memcpy(j.z_t, out->z_t, sizeof(j.z_t));
+      j.ts12 = a->timestamp;
+      j.seq12 = a->scan_seq;
+      j.next12 = a->next_global_id;
+      j.ucfg = *a->update_cfg;
+      j.uin = ui;
+    });
+  } else {
+    for (int k = 0; k < ncl; ++k)
+      if ((rc = live::pmap_clear_tile_launch(pm, clear[k]))) return sub_fail(c, rc, "gcs_pmap_clear_tile", gcs_pmap_last_error(pm));
+    if ((rc = live::pmap_update_launch(pm, lo->active_slots, lo->active_ids, na, out->z_t, a->timestamp, a->scan_seq,
+                                       a->next_global_id, a->update_cfg, &ui)))
+      return sub_fail(c, rc, "gcs_pmap_map_update", gcs_pmap_last_error(pm));
+  }
   lo->next_global_id = a->next_global_id;
   c->live_map = pm;
   mark(6);
@@ -3178,14 +3051,10 @@ int gcs_map_follow(gcs_ctx* c, const gcs_scan_inputs* in, const double* rec) {
   double r[GCS_MAP_REC_LEN];
   memcpy(r, rec, sizeof(r));  // (rec may be the context's own lead_rec)
   memset(c->h_err, 0, sizeof(c->h_err));  // (as gcs_scan: this call's error words only)
-  c->use_direct = c->cfg.mode == GCS_MODE_SCALE && c->direct_buckets && !c->sorted_sticky && c->d_members;
-  struct DirectOff {
-    gcs_ctx* c;
-    ~DirectOff() { c->use_direct = false; }
-  } direct_off{c};
+  DirectScope direct(c);
   for (int pass = 0; pass < 2; ++pass) {
     if (int rc = push_wait(c)) return rc;
-    c->budget_pending = false;
+    if (int rc = stage_budget(c, in->weights_dev, in->n_points, /*toggle=*/true, bin_path_self(c))) return rc;
     if (int rc = stage_points(c, in->xyz_dev, in->point_step, in->timestamps_dev, in->weights_dev, in->n_points,
                               in->scan_start_time, in->scan_end_time, r, nullptr, nullptr, nullptr,
                               /*fold_later=*/true, in->xyz_format == 1))
@@ -3329,48 +3198,42 @@ int gcs_svd3(const double* H, double* U, double* s, double* V) {
   svd3(H, U, s, V);
   return GCS_OK;
 }
+namespace {
+bool imu_odom_args_ok(const gcs_imu_odom_inputs* in, const double* L, const double* h) {
+  return in && L && h && in->m >= 2 && in->stamps && in->gyro && in->accel && in->w_int && in->pose0 && in->pose_pred &&
+         in->mu_prev && in->mu_inc && in->gravity_W && in->Sigma_g && in->Sigma_a && in->odom_pose && in->odom_cov_se3 &&
+         in->odom_twist && in->odom_twist_cov && in->planar_z_sigma > 0.0 && in->planar_vz_sigma > 0.0;
+}
+// the branch's outputs as the C-ABI returns them; ex = [dt_int, dt_imu, omega_avg(3)]; cert may be null
+void pack_imu_odom(const host::ImuOdomOut& io, const double* ex, double* L, double* h, double* cert) {
+  memcpy(L, io.L, sizeof(io.L));
+  memcpy(h, io.h, sizeof(io.h));
+  if (!cert) return;
+  const double v[GCS_IMU_ODOM_CERT_LEN] = {io.trigger, io.ess_weighted, io.kappa, io.transport_sigma, io.imu_scale,
+                                           io.odom_scale, io.mean_reliability, io.odom.nll, io.imu.nll, io.gyro.nll,
+                                           ex[0], ex[1], ex[2], ex[3], ex[4]};
+  memcpy(cert, v, sizeof(v));
+}
+}  // namespace
+
 int gcs_imu_odom_evidence(const gcs_imu_odom_inputs* in, double* L, double* h, double* cert) {
-  if (!in || !L || !h || in->m < 2 || !in->stamps || !in->gyro || !in->accel || !in->w_int || !in->pose0 ||
-      !in->pose_pred || !in->mu_prev || !in->mu_inc || !in->gravity_W || !in->Sigma_g || !in->Sigma_a ||
-      !in->odom_pose || !in->odom_cov_se3 || !in->odom_twist || !in->odom_twist_cov || !(in->planar_z_sigma > 0.0) ||
-      !(in->planar_vz_sigma > 0.0))
-    return GCS_ERR_ARG;
+  if (!imu_odom_args_ok(in, L, h)) return GCS_ERR_ARG;
   host::ImuOdomOut* io = new host::ImuOdomOut();
   double ex[5];
   run_imu_odom(*in, *io, ex);
-  memcpy(L, io->L, sizeof(io->L));
-  memcpy(h, io->h, sizeof(io->h));
-  if (cert) {
-    const double v[GCS_IMU_ODOM_CERT_LEN] = {io->trigger, io->ess_weighted, io->kappa, io->transport_sigma,
-                                             io->imu_scale, io->odom_scale, io->mean_reliability, io->odom.nll,
-                                             io->imu.nll, io->gyro.nll, ex[0], ex[1], ex[2], ex[3], ex[4]};
-    memcpy(cert, v, sizeof(v));
-  }
+  pack_imu_odom(*io, ex, L, h, cert);
   delete io;
   return GCS_OK;
 }
 
 int gcs_imu_odom_evidence_device(gcs_ctx* c, const gcs_imu_odom_inputs* in, double* L, double* h, double* cert) {
   if (!c) return GCS_ERR_ARG;
-  if (!in || !L || !h || in->m < 2 || !in->stamps || !in->gyro || !in->accel || !in->w_int || !in->pose0 ||
-      !in->pose_pred || !in->mu_prev || !in->mu_inc || !in->gravity_W || !in->Sigma_g || !in->Sigma_a ||
-      !in->odom_pose || !in->odom_cov_se3 || !in->odom_twist || !in->odom_twist_cov || !(in->planar_z_sigma > 0.0) ||
-      !(in->planar_vz_sigma > 0.0))
-    return fail(c, GCS_ERR_ARG, "gcs_imu_odom_evidence_device: missing input");
+  if (!imu_odom_args_ok(in, L, h)) return fail(c, GCS_ERR_ARG, "gcs_imu_odom_evidence_device: missing input");
   if (int rc = launch_imu_odom_dev(c, *in)) return rc;
   host::ImuOdomOut* io = new host::ImuOdomOut();
   double ex[5];
   const int rc = finish_imu_odom_dev(c, *io, ex);
-  if (rc == GCS_OK) {
-    memcpy(L, io->L, sizeof(io->L));
-    memcpy(h, io->h, sizeof(io->h));
-    if (cert) {
-      const double v[GCS_IMU_ODOM_CERT_LEN] = {io->trigger, io->ess_weighted, io->kappa, io->transport_sigma,
-                                               io->imu_scale, io->odom_scale, io->mean_reliability, io->odom.nll,
-                                               io->imu.nll, io->gyro.nll, ex[0], ex[1], ex[2], ex[3], ex[4]};
-      memcpy(cert, v, sizeof(v));
-    }
-  }
+  if (rc == GCS_OK) pack_imu_odom(*io, ex, L, h, cert);
   delete io;
   return rc;
 }

@@ -105,11 +105,10 @@ struct PointKernelArgs {
   int* nearest_out;
   double* iz_out;  // 1 / Z per point (per-operator soft-assign materialisation; the record holds w / Z)
   double* t_out;   // budget-selected timestamps (deskew-only stage: n_bins == 0)
-  // the deskew twist in device memory (gcs_scan's pre-launched front: written by k_gate, which the
-  // stream runs right before this kernel); null: xi above
+  // the deskew twist in device memory (device preintegration: written by k_preint, which the stream
+  // runs ahead of this kernel); null: xi above
   const double* xi_dev;
 };
-constexpr uint64_t kGateTimeoutTicks = 20000000ull;  // 200 ms of the 100 MHz constant clock
 
 struct BucketArgs {
   int n_bins, k;
@@ -216,7 +215,6 @@ struct ImuOdomDevArgs {
   uint64_t* dseq;  // device: the calls' sequence counter
 };
 hipError_t launch_imu_odom(const ImuOdomDevArgs& a, hipStream_t s);
-hipError_t launch_gate(const uint64_t* gate, uint64_t seq, double* xi_out, uint32_t* err, hipStream_t s);
 // the hypothesis all-reduce's stage-out (gcs_combine_allreduce): the device sum to a host buffer of n
 // words + [n] sequence number (*dseq + 1, stored back to *dseq) + [n + 1] checksum (mirror_word_hash)
 hipError_t launch_payload_out(const double* src, double* host, int n, uint64_t* dseq, hipStream_t s);

@@ -291,7 +291,7 @@ void k_points(PointKernelArgs a, double* partials) {
     brow[k] = r < a.budget_blocks ? *(const double2*)(a.budget_partials + (size_t)r * pstride<2>())
                                   : make_double2(0.0, 0.0);
   }
-  // the deskew twist: by value, or (pre-launched scan front) from the device word k_gate wrote
+  // the deskew twist: by value, or (device preintegration) from the device words k_preint wrote
   // before this kernel started (stream order makes it visible)
   double xi[6];
 #pragma unroll
@@ -2570,32 +2570,6 @@ hipError_t launch_budget(const BudgetArgs& a, int nblk, hipStream_t s, hipEvent_
   return hipGetLastError();
 }
 
-// ---------------------------------------------------------------- launch gate of the scan front
-// One wave, queued between k_budget and k_points by the pre-launched scan front: lane 0 polls the
-// host gate word (coherent host memory; relaxed system-scope loads are uncached reads, where an
-// acquire would add a cache invalidate per poll) until it holds seq, then copies the deskew twist to
-// device memory for k_points, which the stream starts right behind it.  One poller, one wave: the
-// point kernel itself (~360 registers per lane: one wave per SIMD) is not resident while the host
-// prologue runs, so the previous scan's pushforward keeps the SIMDs (a resident, polling k_points
-// starved it: C2 device wait 77 -> 120 us).  Not opened within kGateTimeoutTicks: zero twist and
-// *err = 1 (gcs_scan fails).
-__global__ __launch_bounds__(64) void k_gate(const uint64_t* gate, uint64_t seq, double* xi_out, uint32_t* err) {
-  if (threadIdx.x != 0) return;
-  const uint64_t t0 = wall_clock64();
-  bool open = false;
-  for (;;) {
-    if (__hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == seq) { open = true; break; }
-    if (wall_clock64() - t0 > kGateTimeoutTicks) break;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  __asm__ volatile("" ::: "memory");
-  for (int k = 0; k < 6; ++k)
-    xi_out[k] = open ? __longlong_as_double((long long)__hip_atomic_load(gate + 1 + k, __ATOMIC_RELAXED,
-                                                                        __HIP_MEMORY_SCOPE_SYSTEM))
-                     : 0.0;
-  if (!open) *err = 1u;
-}
-
 // ---------------------------------------------------------------- hypothesis payload staging
 // The per-scan all-reduce (gcs_combine_allreduce) on the context's combine stream: ncclAllReduce reads
 // the host-packed payload from pinned memory, k_payload_out copies the sum back to a second pinned host
@@ -2638,11 +2612,6 @@ __global__ __launch_bounds__(64) void k_delay(uint32_t us) {
 
 hipError_t launch_delay(int us, hipStream_t s) {
   hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, s, (uint32_t)us);
-  return hipGetLastError();
-}
-
-hipError_t launch_gate(const uint64_t* gate, uint64_t seq, double* xi_out, uint32_t* err, hipStream_t s) {
-  hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, s, gate, seq, xi_out, err);
   return hipGetLastError();
 }
 

@@ -98,7 +98,6 @@ IMU_ODOM_CERT_LEN = 15
 RCCL_ID_BYTES = 128
 DEBUG_SCAN_SPIN_LIMIT, DEBUG_INJECT_SCAN_FAIL = 1, 2
 DEBUG_SORTED_BUCKETS, DEBUG_BUCKET_CAPACITY = 3, 4
-DEBUG_LAUNCH_GATE = 5
 DEBUG_POINT_KERNEL = 6
 DEBUG_DEVICE_PREINT = 7
 DEBUG_PT_CLEAR = 8

@@ -222,18 +222,13 @@ int gcs_ctx_enable_timing(gcs_ctx* ctx, int32_t stage_mask);
  * lowers the direct buckets' row capacity so a test can force the overflow redo (cert[57] = 1). */
 #define GCS_DEBUG_SORTED_BUCKETS 3
 #define GCS_DEBUG_BUCKET_CAPACITY 4
-/* GCS_DEBUG_LAUNCH_GATE: 1 (off by default; GCSLAM_GATE=1) gcs_scan queues its device front before the host prologue and a
- * one-wave gate kernel ahead of k_points waits on the device for the deskew twist; 0 (default) launches
- * the point stage after the prologue;
- * -1 (fault test) never opens the gate, so the gate kernel runs into its timeout and the scan returns
- * GCS_ERR_HIP. */
-#define GCS_DEBUG_LAUNCH_GATE 5
+/* (key 5 is not in use: gcs_ctx_set_debug answers "unknown debug key") */
 /* GCS_DEBUG_POINT_KERNEL != 0: scale-mode scans run the round-3 point kernel (one wave per SIMD)
  * instead of k_points_lean (same arithmetic, bitwise the same outputs; A/B and its parity test). */
 #define GCS_DEBUG_POINT_KERNEL 6
 /* GCS_DEBUG_DEVICE_PREINT != 0 (or GCSLAM_DEVICE_PREINT=1): gcs_scan / gcs_scan_begin compute the
  * IMU window weights and the preintegration (deskew twist) on the device (k_preint) instead of the
- * host prologue; ignored with the launch gate.  A/B knob and its parity test. */
+ * host prologue.  A/B knob and its parity test. */
 #define GCS_DEBUG_DEVICE_PREINT 7
 /* GCS_DEBUG_PT_CLEAR (default 1; GCSLAM_PT_CLEAR=0 turns it off): gcs_scan's k_pt zeroes the next
  * scan's bucket counts and active-flag buffer, so that scan's k_budget only sums the weights; 0 keeps
