@@ -29,6 +29,10 @@
 //                  with per-level histograms, select state and quota
 //   k_kpp_scan     one workgroup over all levels' strips; per-level and total counts, each level's first row
 //   k_kpp_emit     level-major, raster-within-level rows in level-0 coordinates, with kp_level
+//
+// gcs_detect_keypoints_grid replaces the pyramid's per-level select by a fair share among the cells of a grid
+// over each level and hands a level's unused quota on (the definition: G1-G4 in include/gcslam_hip.h): the
+// k_kpg_* kernels further down, one memset and twelve launches whatever n_levels and the number of cells are.
 
 #include <hip/hip_runtime.h>
 
@@ -384,13 +388,17 @@ struct KpPlace {
 
 // One strip of a key image n keys long and Wl wide: the kept pixels in raster order at rows first + (the strip's
 // offsets `base` among the keys above and equal to kth); rows from K on are not written.
+// SPLIT (the grid detector): `key` decides and the response is read from resp_key, the image of the responses' keys.
+template <bool SPLIT = false>
 __device__ __forceinline__ void kp_emit_strip(const uint32_t* __restrict__ key, int strip, int n, uint32_t kth, int need,
                                               int2 base, int first, int K, float* __restrict__ kp_u, float* __restrict__ kp_v,
-                                              float* __restrict__ kp_response, const KpPlace pl) {
+                                              float* __restrict__ kp_response, const KpPlace pl,
+                                              const uint32_t* __restrict__ resp_key = nullptr) {
   __shared__ int2 part[kKpThreads / 64];
   const int t = threadIdx.x;
-  uint32_t k[kKpPerThread];
+  uint32_t k[kKpPerThread], r[kKpPerThread];
   const int i0 = kp_load_keys(key, strip, n, k);
+  if (SPLIT) kp_load_keys(resp_key, strip, n, r);
   int gt = 0, eq = 0;
 #pragma unroll
   for (int j = 0; j < kKpPerThread; ++j) {
@@ -416,7 +424,7 @@ __device__ __forceinline__ void kp_emit_strip(const uint32_t* __restrict__ key, 
           kp_u[pos] = (float)(i % pl.Wl);
           kp_v[pos] = (float)(i / pl.Wl);
         }
-        kp_response[pos] = __uint_as_float(kp_bits_of_key(k[j]));
+        kp_response[pos] = __uint_as_float(kp_bits_of_key(SPLIT ? r[j] : k[j]));
       }
     }
     g += above;
@@ -592,6 +600,245 @@ __global__ __launch_bounds__(kKpThreads) void k_kpp_emit(const uint32_t* __restr
   const KpPlace pl = {Wl, Hl, lv.W[0], lv.H[0], l, o.kp_level};
   kp_emit_strip(key + (size_t)first * kKpStrip, blockIdx.x - first, Wl * Hl, kth, need,
                 make_int2(mine.x - head.x, mine.y - head.y), level_row[l], K, o.kp_u, o.kp_v, o.kp_response, pl);
+}
+
+// ---- the grid of cells (gcs_detect_keypoints_grid; the definition: G1-G4 in include/gcslam_hip.h)
+//
+// The pyramid's resample, score and response kernels as they are, then, whatever n_levels and the number of cells:
+//   k_kpg_rank     one workgroup per cell of any level: the cell's non-zero keys listed in LDS (at most 1024), each
+//                  ranked against the list by (key descending, raster ascending); writes the rank where the key
+//                  is not 0 (into the second key image, which k_kpg_mark then rewrites in place), counts the
+//                  level's cells by their number of survivors (cells_with) and its survivors
+//   k_kpg_plan     one workgroup per level, 8 always: the 8 budgets from the survivor counts and the level's cap
+//                  from its cells_with table (kg_plan), into device memory
+//   k_kpg_mark     per strip: the second key -- 0xffffffff where rank <= t, the key itself where rank = t + 1,
+//                  0 elsewhere -- with its top-byte histogram
+//   k_kpg_hist x 3, k_kpg_count   the select of the b_l largest second keys, the budget read from device memory
+//   k_kpg_scan     as k_kpp_scan, with the six-column level_counts
+//   k_kpg_emit     decides on the second key and takes the response from the first
+// The remainder rule of G3 is the select's own tie handling: the keys of rank t + 1 compete below the 0xffffffff
+// block, ties on the last one to the lowest raster indices.
+
+struct KgGrid {
+  int32_t cell, edge, redistribute, n_cells;
+  int32_t n_cx[kKpMaxLevels], cell0[kKpMaxLevels + 1];
+};
+
+struct KgPlan { int32_t b, t; };   // a level's budget and cap
+
+// The cell (cx, cy) of a W x H level, by one workgroup.  Only pixels of the kept area are read.
+__device__ __forceinline__ void kg_rank_cell(const uint32_t* __restrict__ key, int W, int H, int edge, int cell, int cx, int cy,
+                                             uint32_t* __restrict__ rank, uint32_t* __restrict__ cells_with,
+                                             uint32_t* __restrict__ surv) {
+  __shared__ uint32_t lk[kKgMaxPerCell];
+  __shared__ int la[kKgMaxPerCell];
+  __shared__ int n_list;
+  const int t = threadIdx.x;
+  if (t == 0) n_list = 0;
+  __syncthreads();
+  const int x0 = edge + cx * cell, y0 = edge + cy * cell;
+  const int w = min(cell, W - edge - x0), h = min(cell, H - edge - y0);   // the last column and row: partial cells
+  for (int idx = t; idx < w * h; idx += kKpThreads) {
+    const int at = (y0 + idx / w) * W + x0 + idx % w;
+    const uint32_t k = key[at];
+    if (k) {
+      const int pos = atomicAdd(&n_list, 1);
+      if (pos < kKgMaxPerCell) {   // (no two survivors are neighbours: a cell holds at most 32 x 32 of them)
+        lk[pos] = k;
+        la[pos] = at;
+      }
+    }
+  }
+  __syncthreads();
+  const int n = min(n_list, kKgMaxPerCell);
+  for (int i = t; i < n; i += kKpThreads) {
+    const uint32_t k = lk[i];
+    const int at = la[i];
+    int r = 1;
+    for (int j = 0; j < n; ++j) r += (lk[j] > k) | ((lk[j] == k) & (la[j] < at));
+    rank[at] = (uint32_t)r;
+  }
+  if (t == 0 && n) {
+    atomicAdd(&cells_with[n - 1], 1u);
+    atomicAdd(surv, (uint32_t)n);
+  }
+}
+
+__global__ __launch_bounds__(kKpThreads) void k_kpg_rank(const uint32_t* __restrict__ key, const KpLevels lv, const KgGrid gr,
+                                                         uint32_t* __restrict__ rank, uint32_t* __restrict__ cells_with,
+                                                         uint32_t* __restrict__ surv) {
+  if ((int)blockIdx.x >= gr.n_cells) return;   // (an image without cells still has this launch)
+  const int l = kp_level_at(gr.cell0, lv.n, blockIdx.x);
+  const int c = blockIdx.x - kp_pick(gr.cell0, l), ncx = kp_pick(gr.n_cx, l);
+  const size_t off = (size_t)kp_pick(lv.strip0, l) * kKpStrip;
+  kg_rank_cell(key + off, kp_pick(lv.W, l), kp_pick(lv.H, l), gr.edge, gr.cell, c % ncx, c / ncx, rank + off,
+               cells_with + l * kKgMaxPerCell, surv + l);
+}
+
+// inclusive sums of v over the 256 threads through s; *total: the last one.  s is free again on return.
+__device__ inline uint32_t kg_block_incl(uint32_t v, uint32_t* s, uint32_t* total) {
+  const int t = threadIdx.x;
+  s[t] = v;
+  __syncthreads();
+  for (int off = 1; off < kKpThreads; off <<= 1) {
+    const uint32_t add = t >= off ? s[t - off] : 0u;
+    __syncthreads();
+    s[t] += add;
+    __syncthreads();
+  }
+  const uint32_t incl = s[t];
+  *total = s[kKpThreads - 1];
+  __syncthreads();
+  return incl;
+}
+
+// Level l's budget (G2, from every level's survivors) and cap (G3, from the level's cells_with table), the same
+// in every thread of every workgroup that asks.  Thread t holds n = 4 t + 1 .. 4 t + 4: C(n), the cells with at
+// least n survivors, then G(n) = sum_{q <= n} C(q) = sum_c min(n_c, n); t_l counts the n with C(n) > 0 and
+// G(n) <= b_l, which form a prefix of 1, 2, ...
+__device__ __forceinline__ KgPlan kg_plan(const KpLevels& lv, int redistribute, int l, const uint32_t* __restrict__ surv,
+                                          const uint32_t* __restrict__ cells_with) {
+  __shared__ uint32_t s[kKpThreads];
+  __shared__ int cap;
+  const int t = threadIdx.x;
+  int32_t sv[kKpMaxLevels], b[kKpMaxLevels];
+#pragma unroll
+  for (int m = 0; m < kKpMaxLevels; ++m) sv[m] = (int32_t)surv[m];
+  kg_budgets(lv.quota, sv, redistribute, b);
+  const uint32_t bl = (uint32_t)kp_pick(b, l);
+  if (t == 0) cap = 0;
+  const uint4 q = *(const uint4*)(cells_with + 4 * t);
+  const uint32_t c[4] = {q.x, q.y, q.z, q.w};
+  uint32_t cells;
+  const uint32_t before = kg_block_incl(c[0] + c[1] + c[2] + c[3], s, &cells) - (c[0] + c[1] + c[2] + c[3]);
+  uint32_t C[4];
+  C[0] = cells - before;
+#pragma unroll
+  for (int j = 1; j < 4; ++j) C[j] = C[j - 1] - c[j - 1];
+  uint32_t all;
+  uint32_t G = kg_block_incl(C[0] + C[1] + C[2] + C[3], s, &all) - (C[0] + C[1] + C[2] + C[3]);
+  int mine = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    G += C[j];
+    mine += C[j] > 0 && G <= bl;
+  }
+  if (mine) atomicAdd(&cap, mine);
+  __syncthreads();
+  const KgPlan p = {(int32_t)bl, cap};
+  __syncthreads();
+  return p;
+}
+
+// One strip of level images n keys long: the second key from the first and the rank (held in key2, rewritten in
+// place); ghist2: the 256 bins of the second keys' top byte.
+__device__ __forceinline__ void kg_mark_strip(const uint32_t* __restrict__ key, uint32_t* key2, int strip, int n, int cap,
+                                              uint32_t* __restrict__ ghist2) {
+  __shared__ uint32_t hist[kKpBins];
+  const int t = threadIdx.x;
+  hist[t] = 0;
+  __syncthreads();
+  uint32_t k[kKpPerThread];
+  const int i0 = kp_load_keys(key, strip, n, k);
+  const uint4 lo = *(const uint4*)(key2 + i0), hi = *(const uint4*)(key2 + i0 + 4);
+  const uint32_t r[kKpPerThread] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  uint32_t v[kKpPerThread];
+#pragma unroll
+  for (int j = 0; j < kKpPerThread; ++j) {   // (where the key is 0 the rank was not written: it is not looked at)
+    v[j] = k[j] == 0 ? 0u : r[j] <= (uint32_t)cap ? 0xffffffffu : r[j] == (uint32_t)cap + 1u ? k[j] : 0u;
+    if (v[j]) atomicAdd(&hist[v[j] >> 24], 1u);
+  }
+  *(uint4*)(key2 + i0) = make_uint4(v[0], v[1], v[2], v[3]);
+  *(uint4*)(key2 + i0 + 4) = make_uint4(v[4], v[5], v[6], v[7]);
+  __syncthreads();
+  if (hist[t]) atomicAdd(&ghist2[t], hist[t]);
+}
+
+// One workgroup per level, always 8 of them.  (Rebuilding the plan in every workgroup of k_kpg_mark, the way the
+// select kernels redo their suffix scan, saved this launch and cost 0.010 ms more per call on the MI355X.)
+__global__ __launch_bounds__(kKpThreads) void k_kpg_plan(const KpLevels lv, int redistribute, const uint32_t* __restrict__ surv,
+                                                         const uint32_t* __restrict__ cells_with, KgPlan* __restrict__ plan) {
+  const int l = blockIdx.x;
+  const KgPlan p = kg_plan(lv, redistribute, l, surv, cells_with + l * kKgMaxPerCell);
+  if (threadIdx.x == 0) plan[l] = p;
+}
+
+__global__ __launch_bounds__(kKpThreads) void k_kpg_mark(const uint32_t* __restrict__ key, uint32_t* key2, const KpLevels lv,
+                                                         const KgPlan* __restrict__ plan, uint32_t* __restrict__ ghist2) {
+  const int l = kp_level_at(lv.strip0, lv.n, blockIdx.x), first = kp_pick(lv.strip0, l);
+  const size_t off = (size_t)first * kKpStrip;
+  kg_mark_strip(key + off, key2 + off, blockIdx.x - first, kp_pick(lv.W, l) * kp_pick(lv.H, l), plan[l].t,
+                ghist2 + l * 4 * kKpBins);
+}
+
+__global__ __launch_bounds__(kKpThreads) void k_kpg_hist(const uint32_t* __restrict__ key2, const KpLevels lv, int pass,
+                                                         const KgPlan* __restrict__ plan, uint32_t* __restrict__ ghist2,
+                                                         KpSel* __restrict__ st) {
+  const int l = kp_level_at(lv.strip0, lv.n, blockIdx.x), first = kp_pick(lv.strip0, l);
+  kp_hist_strip(key2 + (size_t)first * kKpStrip, blockIdx.x - first, kp_pick(lv.W, l) * kp_pick(lv.H, l),
+                max(plan[l].b, 1), pass, ghist2 + l * 4 * kKpBins, st + 5 * l);
+}
+
+__global__ __launch_bounds__(kKpThreads) void k_kpg_count(const uint32_t* __restrict__ key2, const KpLevels lv,
+                                                          const KgPlan* __restrict__ plan, const uint32_t* __restrict__ ghist2,
+                                                          KpSel* __restrict__ st, int2* __restrict__ strip_cnt) {
+  const int l = kp_level_at(lv.strip0, lv.n, blockIdx.x), first = kp_pick(lv.strip0, l);
+  kp_count_strip(key2 + (size_t)first * kKpStrip, blockIdx.x - first, kp_pick(lv.W, l) * kp_pick(lv.H, l), plan[l].b,
+                 ghist2 + l * 4 * kKpBins, st + 5 * l, strip_cnt + blockIdx.x);
+}
+
+__global__ __launch_bounds__(kKpScanThreads) void k_kpg_scan(const int2* __restrict__ strip_cnt, const KpLevels lv,
+                                                             const KpSel* __restrict__ st, const KgPlan* __restrict__ plan,
+                                                             const uint32_t* __restrict__ surv, const uint32_t* __restrict__ n_corners,
+                                                             int2* __restrict__ strip_off, int32_t* __restrict__ level_row, int K,
+                                                             gcs_keypoint_grid_outputs o) {
+  __shared__ int n_all;
+  const int t = threadIdx.x;
+  kp_scan_strips(strip_cnt, lv.strip0[kKpMaxLevels], strip_off);
+  if (t == 0) {
+    int row = 0, survivors = 0, corners = 0;
+#pragma unroll
+    for (int l = 0; l < kKpMaxLevels; ++l) {
+      int32_t c[6] = {0, 0, 0, l < lv.n ? lv.quota[l] : 0, 0, 0};
+      if (l < lv.n && lv.strip0[l + 1] > lv.strip0[l]) {   // a level without pixels has no state and no plan
+        const KgPlan p = plan[l];
+        c[0] = kp_kept(st[5 * l + 4], p.b);
+        c[1] = (int32_t)surv[l];
+        c[2] = (int32_t)n_corners[l];
+        c[4] = p.b;
+        c[5] = p.t;
+      }
+      level_row[l] = row;
+      for (int j = 0; j < 6; ++j) o.level_counts[6 * l + j] = c[j];
+      row += c[0]; survivors += c[1]; corners += c[2];
+    }
+    o.counts[0] = row;
+    o.counts[1] = survivors;
+    o.counts[2] = corners;
+    o.counts[3] = lv.n;
+    n_all = row;
+  }
+  __syncthreads();
+  for (int i = n_all + t; i < K; i += kKpScanThreads) {
+    o.kp_u[i] = o.kp_v[i] = o.kp_response[i] = NAN;
+    o.kp_level[i] = -1;
+  }
+}
+
+__global__ __launch_bounds__(kKpThreads) void k_kpg_emit(const uint32_t* __restrict__ key, const uint32_t* __restrict__ key2,
+                                                         const KpLevels lv, const KpSel* __restrict__ st,
+                                                         const KgPlan* __restrict__ plan, const int2* __restrict__ strip_off,
+                                                         const int32_t* __restrict__ level_row, int K, gcs_keypoint_grid_outputs o) {
+  const int l = kp_level_at(lv.strip0, lv.n, blockIdx.x), first = kp_pick(lv.strip0, l);
+  const int Wl = kp_pick(lv.W, l), Hl = kp_pick(lv.H, l);
+  uint32_t kth;
+  int need;
+  kp_cut(st[5 * l + 4], plan[l].b, &kth, &need);
+  const int2 mine = strip_off[blockIdx.x], head = strip_off[first];
+  const KpPlace pl = {Wl, Hl, lv.W[0], lv.H[0], l, o.kp_level};
+  const size_t off = (size_t)first * kKpStrip;
+  kp_emit_strip<true>(key2 + off, blockIdx.x - first, Wl * Hl, kth, need, make_int2(mine.x - head.x, mine.y - head.y),
+                      level_row[l], K, o.kp_u, o.kp_v, o.kp_response, pl, key + off);
 }
 
 // ---- checks and the host build
@@ -1059,6 +1306,328 @@ int gcs_detect_keypoints_pyramid(gcs_keypoint_pyramid_ctx* c, const gcs_keypoint
                      c->level_row, K, o);
   hipLaunchKernelGGL(k_kpp_emit, dim3(n_strips), threads, 0, c->stream, w.key, lv, w.st, w.strip_off, c->level_row, K, o);
   KPPCHK(c, hipGetLastError());
+  return GCS_OK;
+}
+
+}  // extern "C"
+
+// ---- the grid of cells
+
+struct gcs_keypoint_grid_ctx {
+  gcs_keypoint_grid_config cfg{};
+  std::string err;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  void* d_mem = nullptr;
+  size_t clear_bytes = 0;         // both sets of histograms, n_corners, cells_with and the survivor counts
+  int cap_blocks = 0, cap_strips = 0;
+  KpWork w{};                     // as the pyramid's; hist: the response kernel's top-byte histograms
+  uint32_t *key2 = nullptr, *hist2 = nullptr;   // the second key image (first the ranks) and its select's histograms
+  uint32_t *n_corners = nullptr, *cells_with = nullptr, *surv = nullptr;   // per level: 1, 1024, 1
+  KgPlan* plan = nullptr;         // per level
+  int32_t* level_row = nullptr;
+};
+
+namespace {
+int kpg_fail(gcs_keypoint_grid_ctx* c, int code, const std::string& m) {
+  if (c) c->err = m;
+  return code;
+}
+#define KPGCHK(ctx, expr)                                                                          \
+  do {                                                                                            \
+    hipError_t _e = (expr);                                                                       \
+    if (_e != hipSuccess) return kpg_fail((ctx), GCS_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
+  } while (0)
+
+gcs_keypoint_pyramid_config kg_pyramid_config(const gcs_keypoint_grid_config& c) {
+  gcs_keypoint_pyramid_config p;
+  memset(&p, 0, sizeof(p));
+  p.fast_threshold = c.fast_threshold;
+  p.edge_threshold = c.edge_threshold;
+  p.max_keypoints = c.max_keypoints;
+  p.max_width = c.max_width;
+  p.max_height = c.max_height;
+  p.harris_k = c.harris_k;
+  p.n_levels = c.n_levels;
+  p.scale_num = c.scale_num;
+  p.scale_den = c.scale_den;
+  p.device = c.device;
+  return p;
+}
+
+const char* kg_check_config(const gcs_keypoint_grid_config* c) {
+  if (!c) return "null config";
+  const gcs_keypoint_pyramid_config ten = kg_pyramid_config(*c);
+  if (const char* m = kp_check_pyramid_config(&ten)) return m;
+  if (c->cell_size < kKgMinCell || c->cell_size > kKgMaxCell) return "cell_size outside [8, 64]";
+  if (c->redistribute != 0 && c->redistribute != 1) return "redistribute is 0 or 1";
+  return nullptr;
+}
+
+const char* kg_check_call(const gcs_keypoint_grid_config& c, const gcs_keypoint_inputs* in, const gcs_keypoint_grid_outputs* o) {
+  if (!o) return "null inputs or outputs";
+  const gcs_keypoint_pyramid_outputs six = {o->kp_u, o->kp_v, o->kp_response, o->kp_level, o->counts, o->level_counts};
+  return kp_check_pyramid_call(kg_pyramid_config(c), in, &six);
+}
+
+// the cell table of a level table (a level's cells stay below 2^28 / 64, all of them below 2^31)
+KgGrid kg_grid(const gcs_keypoint_grid_config& c, const KpLevels& lv, int32_t n_cy[kKpMaxLevels]) {
+  KgGrid g{};
+  g.cell = c.cell_size;
+  g.edge = c.edge_threshold;
+  g.redistribute = c.redistribute;
+  for (int l = 0; l < kKpMaxLevels; ++l) {
+    int nx = 0, ny = 0;
+    if (lv.strip0[l + 1] > lv.strip0[l]) {
+      nx = kg_cells(lv.W[l], c.edge_threshold, c.cell_size);
+      ny = kg_cells(lv.H[l], c.edge_threshold, c.cell_size);
+      if (nx == 0 || ny == 0) nx = ny = 0;
+    }
+    g.n_cx[l] = nx;
+    n_cy[l] = ny;
+    g.cell0[l + 1] = g.cell0[l] + nx * ny;
+  }
+  g.n_cells = g.cell0[kKpMaxLevels];
+  return g;
+}
+}  // namespace
+
+extern "C" {
+
+int gcs_keypoint_grid_config_defaults(gcs_keypoint_grid_config* c) {
+  if (!c) return GCS_ERR_ARG;
+  gcs_keypoint_pyramid_config ten;
+  gcs_keypoint_pyramid_config_defaults(&ten);
+  memset(c, 0, sizeof(*c));
+  c->fast_threshold = ten.fast_threshold;
+  c->edge_threshold = ten.edge_threshold;
+  c->max_keypoints = ten.max_keypoints;
+  c->max_width = ten.max_width;
+  c->max_height = ten.max_height;
+  c->harris_k = ten.harris_k;
+  c->n_levels = ten.n_levels;
+  c->scale_num = ten.scale_num;
+  c->scale_den = ten.scale_den;
+  c->cell_size = 32;
+  c->redistribute = 1;
+  c->device = 0;
+  return GCS_OK;
+}
+
+int gcs_keypoint_grid_layout(const gcs_keypoint_grid_config* cfg, int32_t width, int32_t height,
+                             int32_t out[GCS_KEYPOINT_MAX_LEVELS][5]) {
+  if (kg_check_config(cfg) || !out || width < 1 || height < 1 || (int64_t)width * height > kKpMaxPixels) return GCS_ERR_ARG;
+  const KpLevels lv = kp_levels(kg_pyramid_config(*cfg), width, height);
+  int32_t n_cy[kKpMaxLevels];
+  const KgGrid g = kg_grid(*cfg, lv, n_cy);
+  for (int l = 0; l < kKpMaxLevels; ++l) {
+    out[l][0] = lv.W[l];
+    out[l][1] = lv.H[l];
+    out[l][2] = lv.quota[l];
+    out[l][3] = g.n_cx[l];
+    out[l][4] = n_cy[l];
+  }
+  return GCS_OK;
+}
+
+const char* gcs_keypoint_grid_last_error(const gcs_keypoint_grid_ctx* c) {
+  return c ? c->err.c_str() : "null keypoint grid context";
+}
+
+int gcs_keypoint_grid_ctx_destroy(gcs_keypoint_grid_ctx* c) {
+  if (!c) return GCS_OK;
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->d_mem) (void)hipFree(c->d_mem);
+  delete c;
+  return GCS_OK;
+}
+
+int gcs_keypoint_grid_ctx_create(const gcs_keypoint_grid_config* cfg, gcs_keypoint_grid_ctx** out) {
+  if (!cfg || !out) return GCS_ERR_ARG;
+  *out = nullptr;
+  if (kg_check_config(cfg)) return GCS_ERR_ARG;
+  auto* c = new gcs_keypoint_grid_ctx();
+  c->cfg = *cfg;
+  c->device = cfg->device;
+  const KpLevels cap = kp_levels(kg_pyramid_config(*cfg), cfg->max_width, cfg->max_height);
+  c->cap_blocks = cap.block0[kKpMaxLevels];
+  c->cap_strips = cap.strip0[kKpMaxLevels];
+  const size_t px = (size_t)c->cap_blocks * kKpThreads, strips = (size_t)c->cap_strips;
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t n_hist = (size_t)kKpMaxLevels * 4 * kKpBins, n_with = (size_t)kKpMaxLevels * kKgMaxPerCell;
+  c->clear_bytes = sizeof(uint32_t) * (2 * n_hist + n_with + 2 * kKpMaxLevels);
+  const size_t z_clear = up(c->clear_bytes), z_st = up(sizeof(KpSel) * 5 * kKpMaxLevels), z_row = up(sizeof(int32_t) * kKpMaxLevels);
+  const size_t z_plan = up(sizeof(KgPlan) * kKpMaxLevels);
+  const size_t z_px = up(px), z_key = up(strips * kKpStrip * sizeof(uint32_t)), z_strip = up(strips * sizeof(int2));
+  if (hipSetDevice(cfg->device) != hipSuccess ||
+      hipMalloc(&c->d_mem, z_clear + z_st + z_row + z_plan + 2 * z_px + 2 * z_key + 2 * z_strip) != hipSuccess) {
+    gcs_keypoint_grid_ctx_destroy(c);
+    return GCS_ERR_HIP;
+  }
+  uint8_t* p = (uint8_t*)c->d_mem;
+  c->w.hist = (uint32_t*)p;
+  c->hist2 = c->w.hist + n_hist;
+  c->cells_with = c->hist2 + n_hist;   // (a multiple of 16 bytes from the allocation's start: read as uint4)
+  c->n_corners = c->cells_with + n_with;
+  c->surv = c->n_corners + kKpMaxLevels;
+  p += z_clear;
+  c->w.st = (KpSel*)p; p += z_st;
+  c->level_row = (int32_t*)p; p += z_row;
+  c->plan = (KgPlan*)p; p += z_plan;
+  c->w.key = (uint32_t*)p; p += z_key;
+  c->key2 = (uint32_t*)p; p += z_key;
+  c->w.strip_cnt = (int2*)p; p += z_strip;
+  c->w.strip_off = (int2*)p; p += z_strip;
+  c->w.grey = p; p += z_px;
+  c->w.score = p;
+  *out = c;
+  return GCS_OK;
+}
+
+int gcs_keypoint_grid_ctx_set_stream(gcs_keypoint_grid_ctx* c, void* stream) {
+  if (!c) return GCS_ERR_ARG;
+  hipStream_t ns = (hipStream_t)stream;
+  if (ns == c->stream) return GCS_OK;
+  KPGCHK(c, hipSetDevice(c->device));
+  KPGCHK(c, hipStreamSynchronize(c->stream));  // the workspace is shared: the old stream's work completes first
+  c->stream = ns;
+  return GCS_OK;
+}
+
+int gcs_detect_keypoints_grid_host(const gcs_keypoint_grid_config* cfg, const gcs_keypoint_inputs* in,
+                                   gcs_keypoint_grid_outputs* out) {
+  if (kg_check_config(cfg) || kg_check_call(*cfg, in, out)) return GCS_ERR_ARG;
+  const int W = in->width, H = in->height, K = cfg->max_keypoints, e = cfg->edge_threshold, cs = cfg->cell_size;
+  const KpLevels lv = kp_levels(kg_pyramid_config(*cfg), W, H);
+  int32_t n_cy[kKpMaxLevels];
+  const KgGrid gr = kg_grid(*cfg, lv, n_cy);
+  // every level's survivors in raster order: raster index and the response's key
+  std::vector<int32_t> at[kKpMaxLevels];
+  std::vector<uint32_t> key[kKpMaxLevels];
+  int32_t surv[kKpMaxLevels] = {}, corners[kKpMaxLevels] = {}, budget[kKpMaxLevels];
+  std::vector<uint8_t> grey;
+  for (int l = 0; l < kKpMaxLevels; ++l) {
+    if (lv.strip0[l + 1] == lv.strip0[l]) continue;   // the level has no pixels
+    const int Wl = lv.W[l], Hl = lv.H[l];
+    grey.assign((size_t)Wl * Hl, 0);
+    for (int y = 0; y < Hl; ++y)
+      for (int x = 0; x < Wl; ++x) {
+        int g;
+        if (l == 0) {
+          const uint8_t* p = in->image + (int64_t)y * in->pitch + (int64_t)in->channels * x;
+          g = in->channels == 3 ? kp_grey(p[0], p[1], p[2]) : p[0];
+        } else {
+          g = in->channels == 3 ? kp_resample_pixel<3>(in->image, in->pitch, W, H, Wl, Hl, x, y)
+                                : kp_resample_pixel<1>(in->image, in->pitch, W, H, Wl, Hl, x, y);
+        }
+        grey[(size_t)y * Wl + x] = (uint8_t)g;
+      }
+    std::vector<uint32_t> bits;
+    int32_t counts[3];
+    // (a cap no level reaches: every survivor comes back)
+    kp_host_level(grey.data(), Wl, Hl, cfg->fast_threshold, e, INT32_MAX, cfg->harris_k, &at[l], &bits, counts);
+    key[l].resize(bits.size());
+    for (size_t i = 0; i < bits.size(); ++i) key[l][i] = kp_key_of_bits(bits[i]);
+    surv[l] = counts[1];
+    corners[l] = counts[2];
+  }
+  kg_budgets(lv.quota, surv, cfg->redistribute, budget);
+  int32_t sum[3] = {0, 0, 0};
+  int m = 0;
+  for (int l = 0; l < kKpMaxLevels; ++l) {
+    const int Wl = lv.W[l], Hl = lv.H[l], n = (int)at[l].size(), b = budget[l];
+    int t = 0, kept = 0;
+    if (n) {
+      // G3: the survivors by (cell, key descending, raster ascending); a survivor's rank is its place in its cell
+      const int ncx = gr.n_cx[l];
+      std::vector<int32_t> cell(n), order(n), rank(n);
+      for (int i = 0; i < n; ++i) {
+        cell[i] = ((at[l][i] / Wl - e) / cs) * ncx + (at[l][i] % Wl - e) / cs;
+        order[i] = i;
+      }
+      const std::vector<uint32_t>& k = key[l];
+      std::sort(order.begin(), order.end(), [&](int32_t a, int32_t c2) {
+        if (cell[a] != cell[c2]) return cell[a] < cell[c2];
+        if (k[a] != k[c2]) return k[a] > k[c2];
+        return a < c2;   // (the list is in raster order)
+      });
+      std::vector<int32_t> cells_with(kKgMaxPerCell, 0);
+      for (int i = 0, r = 0; i < n; ++i) {
+        r = (i && cell[order[i]] == cell[order[i - 1]]) ? r + 1 : 1;
+        rank[order[i]] = r;
+        if (i + 1 == n || cell[order[i + 1]] != cell[order[i]]) ++cells_with[r - 1];
+      }
+      int64_t at_t;
+      t = kg_cap_host(cells_with.data(), b, &at_t);
+      const int rem = (int)(b - at_t);
+      // the remainder: the rem best of rank t + 1 by (key descending, raster ascending)
+      std::vector<int32_t> next;
+      for (int i = 0; i < n; ++i)
+        if (rank[i] == t + 1) next.push_back(i);
+      std::sort(next.begin(), next.end(), [&](int32_t a, int32_t c2) { return k[a] != k[c2] ? k[a] > k[c2] : a < c2; });
+      std::vector<uint8_t> keep(n, 0);
+      for (int i = 0; i < n; ++i) keep[i] = rank[i] <= t;
+      for (int i = 0; i < rem && i < (int)next.size(); ++i) keep[next[i]] = 1;
+      for (int i = 0; i < n; ++i) {
+        if (!keep[i]) continue;
+        ++kept;
+        if (m >= K) continue;   // (the budgets sum to at most K)
+        out->kp_u[m] = kp_level0_coord(at[l][i] % Wl, W, Wl);
+        out->kp_v[m] = kp_level0_coord(at[l][i] / Wl, H, Hl);
+        const uint32_t bits = kp_bits_of_key(k[i]);
+        memcpy(&out->kp_response[m], &bits, 4);
+        out->kp_level[m] = l;
+        ++m;
+      }
+    }
+    const int32_t row[6] = {kept, surv[l], corners[l], l < lv.n ? lv.quota[l] : 0, b, t};
+    for (int j = 0; j < 6; ++j) out->level_counts[6 * l + j] = row[j];
+    for (int j = 0; j < 3; ++j) sum[j] += row[j];
+  }
+  for (int i = m; i < K; ++i) {
+    out->kp_u[i] = out->kp_v[i] = out->kp_response[i] = NAN;
+    out->kp_level[i] = -1;
+  }
+  for (int j = 0; j < 3; ++j) out->counts[j] = sum[j];
+  out->counts[3] = lv.n;
+  return GCS_OK;
+}
+
+int gcs_detect_keypoints_grid(gcs_keypoint_grid_ctx* c, const gcs_keypoint_inputs* in, gcs_keypoint_grid_outputs* out) {
+  if (!c) return GCS_ERR_ARG;
+  if (const char* m = kg_check_call(c->cfg, in, out)) return kpg_fail(c, GCS_ERR_ARG, m);
+  const KpLevels lv = kp_levels(kg_pyramid_config(c->cfg), in->width, in->height);
+  const int n_blocks = lv.block0[kKpMaxLevels], n_tiles = lv.tile0[kKpMaxLevels], n_strips = lv.strip0[kKpMaxLevels];
+  if (n_blocks > c->cap_blocks || n_strips > c->cap_strips) return kpg_fail(c, GCS_ERR_ARG, "the image's levels exceed the workspace");
+  int32_t n_cy[kKpMaxLevels];
+  const KgGrid gr = kg_grid(c->cfg, lv, n_cy);
+  KPGCHK(c, hipSetDevice(c->device));
+  const int K = c->cfg.max_keypoints;
+  const KpWork& w = c->w;
+  KPGCHK(c, hipMemsetAsync(w.hist, 0, c->clear_bytes, c->stream));
+  const dim3 threads(kKpThreads);
+  if (in->channels == 3)
+    hipLaunchKernelGGL(k_kpp_resample<3>, dim3(n_blocks), threads, 0, c->stream, in->image, in->pitch, lv, w.grey);
+  else
+    hipLaunchKernelGGL(k_kpp_resample<1>, dim3(n_blocks), threads, 0, c->stream, in->image, in->pitch, lv, w.grey);
+  hipLaunchKernelGGL(k_kpp_score, dim3(n_tiles), threads, 0, c->stream, w.grey, lv, c->cfg.fast_threshold, w.score, c->n_corners);
+  hipLaunchKernelGGL(k_kpp_response, dim3(n_tiles), threads, 0, c->stream, w.score, w.grey, lv, c->cfg.edge_threshold,
+                     c->cfg.harris_k, w.key, w.hist);
+  hipLaunchKernelGGL(k_kpg_rank, dim3(std::max(gr.n_cells, 1)), threads, 0, c->stream, w.key, lv, gr, c->key2, c->cells_with,
+                     c->surv);
+  hipLaunchKernelGGL(k_kpg_plan, dim3(kKpMaxLevels), threads, 0, c->stream, lv, gr.redistribute, c->surv, c->cells_with,
+                     c->plan);
+  hipLaunchKernelGGL(k_kpg_mark, dim3(n_strips), threads, 0, c->stream, w.key, c->key2, lv, c->plan, c->hist2);
+  for (int pass = 1; pass <= 3; ++pass)
+    hipLaunchKernelGGL(k_kpg_hist, dim3(n_strips), threads, 0, c->stream, c->key2, lv, pass, c->plan, c->hist2, w.st);
+  hipLaunchKernelGGL(k_kpg_count, dim3(n_strips), threads, 0, c->stream, c->key2, lv, c->plan, c->hist2, w.st, w.strip_cnt);
+  const gcs_keypoint_grid_outputs o = *out;
+  hipLaunchKernelGGL(k_kpg_scan, dim3(1), dim3(kKpScanThreads), 0, c->stream, w.strip_cnt, lv, w.st, c->plan, c->surv,
+                     c->n_corners, w.strip_off, c->level_row, K, o);
+  hipLaunchKernelGGL(k_kpg_emit, dim3(n_strips), threads, 0, c->stream, w.key, c->key2, lv, w.st, c->plan, w.strip_off,
+                     c->level_row, K, o);
+  KPGCHK(c, hipGetLastError());
   return GCS_OK;
 }
 

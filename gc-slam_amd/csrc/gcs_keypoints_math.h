@@ -170,4 +170,47 @@ GCS_HD float kp_level0_coord(int x, int W, int W_l) {
   return (float)(q - 0.5);
 }
 
+// ---- the grid of cells (gcs_detect_keypoints_grid): cell counts, budgets, the cap
+
+constexpr int kKgMinCell = 8, kKgMaxCell = 64;
+constexpr int kKgMaxPerCell = 1024;   // strict 3 x 3 suppression: at most ceil(64 / 2)^2 survivors in a cell
+
+// n_cx of a level W_l wide: the cells that cover [e, W_l - e), the last one maybe partial; 0 without such pixels
+GCS_HD int kg_cells(int W_l, int edge, int cell_size) {
+  const int64_t kept = (int64_t)W_l - 2 * (int64_t)edge;
+  return kept > 0 ? (int)((kept + cell_size - 1) / cell_size) : 0;
+}
+
+// b_l = min(quota_l, s_l); with `redistribute` what the levels leave of their quotas goes to the levels that
+// have survivors beyond theirs, the finest first
+GCS_HD void kg_budgets(const int32_t* quota, const int32_t* surv, int redistribute, int32_t* b) {
+  int64_t spare = 0;
+  for (int l = 0; l < kKpMaxLevels; ++l) {
+    b[l] = quota[l] < surv[l] ? quota[l] : surv[l];
+    spare += quota[l] - b[l];
+  }
+  if (!redistribute) return;
+  for (int l = 0; l < kKpMaxLevels; ++l) {
+    const int64_t room = surv[l] - b[l], give = spare < room ? spare : room;
+    b[l] += (int32_t)give;
+    spare -= give;
+  }
+}
+
+// The cap t of a level from cells_with[n - 1], the number of its cells that hold exactly n survivors
+// (1 <= n <= 1024): the largest t with sum_c min(n_c, t) <= b, no larger than max_c n_c; *kept_at_t: that sum.
+inline int kg_cap_host(const int32_t* cells_with, int64_t b, int64_t* kept_at_t) {
+  int t = 0;
+  int64_t sum = 0;
+  for (;;) {
+    int64_t deeper = 0;   // the cells with more than t survivors
+    for (int n = t + 1; n <= kKgMaxPerCell; ++n) deeper += cells_with[n - 1];
+    if (deeper == 0 || sum + deeper > b) break;
+    sum += deeper;
+    ++t;
+  }
+  *kept_at_t = sum;
+  return t;
+}
+
 }  // namespace gcs

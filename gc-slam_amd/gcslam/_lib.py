@@ -226,6 +226,16 @@ class GcsKeypointPyramidOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("kp_u", "kp_v", "kp_response", "kp_level", "counts", "level_counts")]
 
 
+class GcsKeypointGridConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("fast_threshold", "edge_threshold", "max_keypoints", "max_width",
+                                         "max_height")] + [("harris_k", C.c_double)] + \
+               [(n, C.c_int32) for n in ("n_levels", "scale_num", "scale_den", "cell_size", "redistribute", "device")]
+
+
+class GcsKeypointGridOutputs(C.Structure):   # level_counts: KEYPOINT_MAX_LEVELS x 6
+    _fields_ = [(n, C.c_void_p) for n in ("kp_u", "kp_v", "kp_response", "kp_level", "counts", "level_counts")]
+
+
 class GcsRenderConfig(C.Structure):
     _fields_ = [("tile_size", C.c_int32), ("max_splats_per_tile", C.c_int32), ("fbm_octaves", C.c_int32),
                 ("fbm_gain", C.c_double), ("opacity_gamma", C.c_double), ("logdet0", C.c_double), ("eps", C.c_double),
@@ -504,6 +514,15 @@ _SIGS = [
     ("gcs_detect_keypoints_pyramid_host", C.c_int, [C.POINTER(GcsKeypointPyramidConfig), C.POINTER(GcsKeypointInputs),
                                                     C.POINTER(GcsKeypointPyramidOutputs)]),
     ("gcs_keypoint_pyramid_layout", C.c_int, [C.POINTER(GcsKeypointPyramidConfig), C.c_int32, C.c_int32, C.c_void_p]),
+    ("gcs_keypoint_grid_config_defaults", C.c_int, [C.POINTER(GcsKeypointGridConfig)]),
+    ("gcs_keypoint_grid_ctx_create", C.c_int, [C.POINTER(GcsKeypointGridConfig), C.POINTER(C.c_void_p)]),
+    ("gcs_keypoint_grid_ctx_destroy", C.c_int, [C.c_void_p]),
+    ("gcs_keypoint_grid_last_error", C.c_char_p, [C.c_void_p]),
+    ("gcs_keypoint_grid_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gcs_detect_keypoints_grid", C.c_int, [C.c_void_p, C.POINTER(GcsKeypointInputs), C.POINTER(GcsKeypointGridOutputs)]),
+    ("gcs_detect_keypoints_grid_host", C.c_int, [C.POINTER(GcsKeypointGridConfig), C.POINTER(GcsKeypointInputs),
+                                                 C.POINTER(GcsKeypointGridOutputs)]),
+    ("gcs_keypoint_grid_layout", C.c_int, [C.POINTER(GcsKeypointGridConfig), C.c_int32, C.c_int32, C.c_void_p]),
     ("gcs_render_config_defaults", C.c_int, [C.POINTER(GcsRenderConfig)]),
     ("gcs_render_ctx_create", C.c_int, [C.POINTER(GcsRenderConfig), C.POINTER(C.c_void_p)]),
     ("gcs_render_ctx_destroy", C.c_int, [C.c_void_p]),

@@ -8,7 +8,11 @@ the (u, v, response) triple gcslam.visual takes as `keypoints`, device to device
 
 PyramidDetector (gcs_detect_keypoints_pyramid) runs the same detector over a scale pyramid -- n_levels exact
 pixel-area resamples of the grey image at the rational scale scale_num / scale_den, a fixed quota of
-max_keypoints per level -- and reports every keypoint in level-0 pixel coordinates with its level."""
+max_keypoints per level -- and reports every keypoint in level-0 pixel coordinates with its level.
+
+GridDetector (gcs_detect_keypoints_grid) is the pyramid detector with each level's selection replaced by a fair
+share among the cells of a grid over the level, so that the kept keypoints spread over the image, and with a
+level's unused quota handed on to the levels that have survivors to spare (finest first)."""
 
 from __future__ import annotations
 
@@ -263,11 +267,11 @@ class PyramidKeypoints(Keypoints):
     level_counts = ((0, 0, 0, 0),) * MAX_LEVELS
 
 
-def _pyramid_result(rows, level, words, n=None):
+def _pyramid_result(rows, level, words, n=None, cols=4):
     out = PyramidKeypoints(r if n is None else r[:n] for r in rows)
     out.level = level if n is None else level[:n]
     out.counts = tuple(int(v) for v in words[:4])
-    out.level_counts = tuple(tuple(int(v) for v in words[4 + 4 * l:8 + 4 * l]) for l in range(MAX_LEVELS))
+    out.level_counts = tuple(tuple(int(v) for v in words[4 + cols * l:4 + cols * (l + 1)]) for l in range(MAX_LEVELS))
     return out
 
 
@@ -380,3 +384,165 @@ def detect_keypoints_pyramid_host(image, config: Optional[PyramidConfig] = None,
     if rc != 0:
         raise ValueError(f"gcs_detect_keypoints_pyramid_host failed ({rc})")
     return _pyramid_result(rows, level, words.tolist(), int(words[0]) if trim else None)
+
+
+# ---- the grid of cells
+
+@dataclass(frozen=True)
+class GridConfig:
+    """gcs_keypoint_grid_config: PyramidConfig's fields, the side of a cell in level pixels and whether a level's
+    unused quota is handed on."""
+    fast_threshold: int = 20
+    edge_threshold: int = 31
+    max_keypoints: int = 4096
+    max_width: int = 1920
+    max_height: int = 1080
+    harris_k: float = 0.04
+    n_levels: int = 8
+    scale_num: int = 6
+    scale_den: int = 5
+    cell_size: int = 32
+    redistribute: bool = True
+
+
+GRID_COLUMNS = 6   # level_counts: n_keypoints, n_survivors, n_corners, quota, budget, cap
+_GRID_WORDS = 4 + GRID_COLUMNS * MAX_LEVELS
+
+
+def grid_config_struct(config: Optional[GridConfig] = None, device: int = 0) -> "L.GcsKeypointGridConfig":
+    """gcs_keypoint_grid_config of a GridConfig."""
+    config = config or GridConfig()
+    c = L.GcsKeypointGridConfig()
+    L.check(L.load().gcs_keypoint_grid_config_defaults(C.byref(c)), None, "gcs_keypoint_grid_config_defaults")
+    for f in fields(config):
+        setattr(c, f.name, getattr(config, f.name))
+    c.device = int(device)
+    return c
+
+
+def grid_config_defaults() -> GridConfig:
+    """gcs_keypoint_grid_config_defaults as a GridConfig."""
+    c = L.GcsKeypointGridConfig()
+    L.check(L.load().gcs_keypoint_grid_config_defaults(C.byref(c)), None, "gcs_keypoint_grid_config_defaults")
+    got = {f.name: getattr(c, f.name) for f in fields(GridConfig)}
+    return GridConfig(**dict(got, redistribute=bool(got["redistribute"])))
+
+
+def grid_layout(config: Optional[GridConfig], width: int, height: int):
+    """gcs_keypoint_grid_layout: an (8, 5) int32 array of W_l, H_l, quota_l, n_cx, n_cy."""
+    out = np.zeros((MAX_LEVELS, 5), np.int32)
+    c = grid_config_struct(config, 0)
+    if L.load().gcs_keypoint_grid_layout(C.byref(c), int(width), int(height), out.ctypes.data) != 0:
+        raise ValueError("gcs_keypoint_grid_layout: a config or an image size outside its range")
+    return out
+
+
+class GridDetector(PyramidDetector):
+    """A gcs_keypoint_grid_ctx: the pyramid's packed workspace and a second key image for images up to
+    config.max_width x config.max_height on one GPU.  queue, detect and close as PyramidDetector's; the result's
+    level_counts has six columns (n_keypoints, n_survivors, n_corners, quota, budget, cap)."""
+
+    def __init__(self, config: Optional[GridConfig] = None, device: int = 0):
+        self.config = config or GridConfig()
+        self.lib = L.load()
+        c = grid_config_struct(self.config, device)
+        h = C.c_void_p()
+        rc = self.lib.gcs_keypoint_grid_ctx_create(C.byref(c), C.byref(h))
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"gcs_keypoint_grid_ctx_create failed ({rc})")
+        self.h, self.device = h, int(device)
+        self._pinned = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gcs_keypoint_grid_ctx_destroy(self.h)
+            self.h = None
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            msg = self.lib.gcs_keypoint_grid_last_error(self.h).decode(errors="replace")
+            raise (ValueError if rc in (-1, -3) else RuntimeError)(f"{what} failed ({rc}): {msg}")
+
+    def queue(self, image):
+        """gcs_detect_keypoints_grid on the current torch stream, without waiting: ((u, v, response) of all
+        max_keypoints rows, NaN beyond the count; the rows' levels, -1 beyond it; the 52 device words of counts
+        and level_counts)."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        x, H, W, ch = self._image(image)
+        K = int(self.config.max_keypoints)
+        buf = torch.empty(4 * K + _GRID_WORDS, dtype=torch.float32, device=dev)
+        level, words = buf[3 * K:4 * K].view(torch.int32), buf[4 * K:].view(torch.int32)
+        i = _inputs_struct(x.data_ptr(), ch, x.stride(0), W, H)
+        o = L.GcsKeypointGridOutputs()
+        o.kp_u, o.kp_v, o.kp_response, o.kp_level = (buf[j * K:].data_ptr() for j in range(4))
+        o.counts, o.level_counts = words.data_ptr(), words[4:].data_ptr()
+        self._chk(self.lib.gcs_keypoint_grid_ctx_set_stream(
+            self.h, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gcs_keypoint_grid_ctx_set_stream")
+        self._chk(self.lib.gcs_detect_keypoints_grid(self.h, C.byref(i), C.byref(o)), "gcs_detect_keypoints_grid")
+        return tuple(buf[j * K:(j + 1) * K] for j in range(3)), level, words
+
+    def detect(self, image) -> PyramidKeypoints:
+        """One image's keypoints, spread over the grid: as PyramidDetector.detect, with the six-column
+        level_counts.  The call waits once, for the 208 bytes of counts and level_counts."""
+        import torch
+        rows, level, words = self.queue(image)
+        if self._pinned is None:
+            self._pinned = torch.empty(_GRID_WORDS, dtype=torch.int32).pin_memory()
+        self._pinned.copy_(words, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(torch.device(f"cuda:{self.device}")))
+        ev.synchronize()
+        w = self._pinned.tolist()
+        return _pyramid_result(rows, level, w, w[0], GRID_COLUMNS)
+
+
+_grid_detectors = {}
+
+
+def _grid_detector_for(config: GridConfig, device: int, height: int, width: int) -> GridDetector:
+    """The cached grid detector of (config, device); its capacity grows to the largest image seen."""
+    key = (replace(config, max_width=0, max_height=0), int(device))
+    d = _grid_detectors.get(key)
+    if d is None or d.h is None or d.config.max_width < width or d.config.max_height < height:
+        have = d.config if d is not None else config
+        if d is not None:
+            d.close()
+        d = _grid_detectors[key] = GridDetector(
+            replace(config, max_width=max(have.max_width, config.max_width, width),
+                    max_height=max(have.max_height, config.max_height, height)), device)
+    return d
+
+
+def detect_keypoints_grid(image, config: Optional[GridConfig] = None, device: int = 0) -> PyramidKeypoints:
+    """GridDetector.detect on a cached detector of (config, device)."""
+    H, W, _ = _shape(image.shape)
+    return _grid_detector_for(config or GridConfig(), device, H, W).detect(image)
+
+
+def detect_keypoints_grid_host(image, config: Optional[GridConfig] = None, pitch: Optional[int] = None,
+                               shape=None, trim: bool = True) -> PyramidKeypoints:
+    """The same steps through gcs_detect_keypoints_grid_host: numpy in and out, no device.  Arguments as
+    detect_keypoints_host's."""
+    config = config or GridConfig()
+    a = np.ascontiguousarray(image, np.uint8)
+    if pitch is None:
+        H, W, ch = _shape(a.shape)
+        pitch = W * ch
+    else:
+        H, W, ch = (int(v) for v in shape)
+        if a.ndim != 1 or H < 1 or a.size < (H - 1) * pitch + W * ch:
+            raise ValueError("image: a flat buffer of at least (H - 1) * pitch + W * channels bytes")
+    c = grid_config_struct(replace(config, max_width=max(config.max_width, W), max_height=max(config.max_height, H)), 0)
+    K = int(config.max_keypoints)
+    rows = [np.empty(max(K, 0), np.float32) for _ in range(3)]
+    level = np.empty(max(K, 0), np.int32)
+    words = np.zeros(_GRID_WORDS, np.int32)
+    i = _inputs_struct(a.ctypes.data, ch, pitch, W, H)
+    o = L.GcsKeypointGridOutputs()
+    o.kp_u, o.kp_v, o.kp_response = (r.ctypes.data for r in rows)
+    o.kp_level, o.counts, o.level_counts = level.ctypes.data, words.ctypes.data, words[4:].ctypes.data
+    rc = L.load().gcs_detect_keypoints_grid_host(C.byref(c), C.byref(i), C.byref(o))
+    if rc != 0:
+        raise ValueError(f"gcs_detect_keypoints_grid_host failed ({rc})")
+    return _pyramid_result(rows, level, words.tolist(), int(words[0]) if trim else None, GRID_COLUMNS)

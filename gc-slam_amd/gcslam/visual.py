@@ -20,7 +20,8 @@ import numpy as np
 
 from . import _lib as L
 from .camera import CameraFrame, DepthFusionConfig, PinholeIntrinsics, _DeviceFeatures
-from .keypoints import KeypointConfig, PyramidConfig, detect_keypoints, detect_keypoints_pyramid
+from .keypoints import (GridConfig, KeypointConfig, PyramidConfig, detect_keypoints, detect_keypoints_grid,
+                        detect_keypoints_pyramid)
 
 _MODES = {"nearest": L.VF_NEAREST, "median3": L.VF_MEDIAN3, "median5": L.VF_MEDIAN5, "hex": L.VF_HEX}
 _MODELS = {"linear": L.VF_DEPTH_LINEAR, "quadratic": L.VF_DEPTH_QUADRATIC}
@@ -170,14 +171,14 @@ class VisualFeatureExtractor:
         return x
 
     def extract(self, depth, rgb, keypoints, intrinsics: PinholeIntrinsics, want_diag: bool = False,
-                trim: bool = True, keypoint_config: Optional[Union[KeypointConfig, PyramidConfig]] = None) -> _DeviceFeatures:
+                trim: bool = True, keypoint_config: Optional[Union[KeypointConfig, PyramidConfig, GridConfig]] = None) -> _DeviceFeatures:
         """One frame's features as gcslam.camera's device feature dict, on the current torch stream and
         without waiting for it.  depth: (H, W) float32 or uint16 (metres = value * depth_scale), rgb:
         (H, W, 3) uint8 or None; torch device tensors, or numpy arrays (uploaded once).  keypoints: (n, 3)
         u, v, response or three arrays.  The dict's arrays hold .count = min(n, max_features) rows (trim
         False: all max_features, zeros beyond count); .diag (want_diag) the per-feature diagnostics.
         keypoints None: detected from rgb (gcslam.keypoints.detect_keypoints with keypoint_config, or with a
-        PyramidConfig detect_keypoints_pyramid) on the same stream; that route waits once, for the detector's
+        PyramidConfig detect_keypoints_pyramid, with a GridConfig detect_keypoints_grid) on the same stream; that route waits once, for the detector's
         counts words."""
         import torch
         if keypoints is None and rgb is None:
@@ -193,7 +194,9 @@ class VisualFeatureExtractor:
             if tuple(c.shape) != (H, W, 3):
                 raise ValueError(f"rgb: shape {tuple(c.shape)}, expected {(H, W, 3)}")
         if keypoints is None:
-            if isinstance(keypoint_config, PyramidConfig):
+            if isinstance(keypoint_config, GridConfig):
+                keypoints = detect_keypoints_grid(c, keypoint_config, self.device)
+            elif isinstance(keypoint_config, PyramidConfig):
                 keypoints = detect_keypoints_pyramid(c, keypoint_config, self.device)
             else:
                 keypoints = detect_keypoints(c, keypoint_config, self.device)
@@ -235,7 +238,7 @@ def _extractor_for(config, device) -> VisualFeatureExtractor:
 
 def extract_visual_features(depth, rgb, keypoints, intrinsics: PinholeIntrinsics,
                             config: Optional[VisualFeatureConfig] = None, device: int = 0, want_diag: bool = False,
-                            trim: bool = True, keypoint_config: Optional[Union[KeypointConfig, PyramidConfig]] = None) -> _DeviceFeatures:
+                            trim: bool = True, keypoint_config: Optional[Union[KeypointConfig, PyramidConfig, GridConfig]] = None) -> _DeviceFeatures:
     """VisualFeatureExtractor.extract on a cached extractor of (config, device)."""
     return _extractor_for(config or VisualFeatureConfig(), device).extract(depth, rgb, keypoints, intrinsics,
                                                                            want_diag=want_diag, trim=trim,
@@ -286,7 +289,7 @@ def camera_frame_from_rgbd(depth, rgb, keypoints, intrinsics: PinholeIntrinsics,
                            timestamp_sec: float, config: Optional[VisualFeatureConfig] = None,
                            fusion_config: Optional[DepthFusionConfig] = None, device: int = 0,
                            want_diag: bool = False, max_candidates: int = 1024,
-                           keypoint_config: Optional[Union[KeypointConfig, PyramidConfig]] = None) -> CameraFrame:
+                           keypoint_config: Optional[Union[KeypointConfig, PyramidConfig, GridConfig]] = None) -> CameraFrame:
     """on_rgbd after detectAndCompute, the VisualFeatureBatch and _feature_batch_to_list in one step: the
     frame's features extracted on the GPU and held there in a CameraFrame for
     process_scan_single_hypothesis(camera_batch=..., camera_batch_policy="use").  keypoints None: detectAndCompute's

@@ -930,6 +930,72 @@ int gcs_detect_keypoints_pyramid_host(const gcs_keypoint_pyramid_config* cfg, co
 int gcs_keypoint_pyramid_layout(const gcs_keypoint_pyramid_config* cfg, int32_t width, int32_t height,
                                 int32_t out[GCS_KEYPOINT_MAX_LEVELS][3]);
 
+/* Keypoints spread over a grid of cells: the pyramid detector above with its per-level selection (the second
+ * half of P4) replaced by a fair share among the cells of each level, and, on request, a level's unused quota
+ * handed on (what cv::ORB's spreading of its keypoints over the image does for the map; the definition is
+ * the project's own, integer-exact wherever the two above are, and claims no parity with cv::ORB).  Steps P1-P3
+ * and the quotas of P4 are as above.  With e = edge_threshold, s_l the survivors of level l after step 4:
+ *  G1. cells: level l's kept area e <= x < W_l - e, e <= y < H_l - e is cut into cells of cell_size x cell_size
+ *      level pixels anchored at (e, e): cx = (x - e) / cell_size, cy likewise, n_cx = ceil((W_l - 2 e) /
+ *      cell_size), n_cy likewise, cell id cy n_cx + cx.  The last column and row may be partial.  A level with
+ *      W_l <= 2 e or H_l <= 2 e has no cells and no keypoints.  Step 3 leaves at most ceil(cell_size / 2)^2
+ *      <= 1024 survivors in a cell.
+ *  G2. budgets: b_l = min(quota_l, s_l).  With redistribute: spare = sum_l (quota_l - b_l); then for l = 0, 1,
+ *      ... in this order give = min(spare, s_l - b_l), b_l += give, spare -= give.  So sum_l b_l =
+ *      min(K, sum_l s_l), the finest levels filled first.
+ *  G3. fair share: within a cell the survivors are ordered by (response descending, raster index y W_l + x
+ *      ascending); survivor i has rank r_i = 1, 2, ... in its cell.  With n_c the survivors of cell c, the cap
+ *      t_l is the largest t >= 0 with sum_c min(n_c, t) <= b_l, taken no larger than max_c n_c.  Every survivor
+ *      with r_i <= t_l is kept; rem_l = b_l - sum_c min(n_c, t_l); of the survivors with r_i = t_l + 1 the rem_l
+ *      best by (response descending, raster index ascending) over the whole level -- step 6's order and tie
+ *      rule -- are kept as well.  Exactly b_l keypoints are kept, and with b_l at least the number of non-empty
+ *      cells every non-empty cell keeps one.
+ *  G4. output: as P5, rows in (level, raster index) order, rows [n_keypoints, max_keypoints) NaN and -1.
+ * With redistribute = 0 and every level's kept area inside one cell, and whenever s_l <= quota_l on every
+ * level, the rows, counts and the first four columns of level_counts equal gcs_detect_keypoints_pyramid's.
+ * The number of kernel launches of a call depends neither on n_levels nor on the number of cells.  Calls on
+ * one context must be serialised. */
+typedef struct gcs_keypoint_grid_ctx gcs_keypoint_grid_ctx;
+
+typedef struct {
+  int32_t fast_threshold;        /* the ten fields of gcs_keypoint_pyramid_config, same defaults and ranges */
+  int32_t edge_threshold;
+  int32_t max_keypoints;
+  int32_t max_width, max_height;
+  double harris_k;
+  int32_t n_levels;
+  int32_t scale_num, scale_den;
+  int32_t cell_size;             /* 32; 8 .. 64 level pixels */
+  int32_t redistribute;          /* 1; 0: an unused share is not handed on, 1: G2's second half */
+  int32_t device;
+} gcs_keypoint_grid_config;
+
+typedef struct {
+  float *kp_u, *kp_v, *kp_response;   /* max_keypoints each */
+  int32_t* kp_level;             /* max_keypoints */
+  int32_t* counts;               /* 4: n_keypoints, n_survivors, n_corners (each summed over the levels), n_levels */
+  int32_t* level_counts;         /* GCS_KEYPOINT_MAX_LEVELS x 6: per level n_keypoints, n_survivors, n_corners,
+                                    quota_l, b_l, t_l; rows of levels >= n_levels are zero */
+} gcs_keypoint_grid_outputs;
+
+int gcs_keypoint_grid_config_defaults(gcs_keypoint_grid_config* cfg);
+/* GCS_ERR_ARG, before any device call, for a config outside the ranges above. */
+int gcs_keypoint_grid_ctx_create(const gcs_keypoint_grid_config* cfg, gcs_keypoint_grid_ctx** out);
+int gcs_keypoint_grid_ctx_destroy(gcs_keypoint_grid_ctx* ctx);
+const char* gcs_keypoint_grid_last_error(const gcs_keypoint_grid_ctx* ctx);
+int gcs_keypoint_grid_ctx_set_stream(gcs_keypoint_grid_ctx* ctx, void* stream);
+/* Queues its kernels on the context's stream and returns; every output is a device array.  Refusals as
+ * gcs_detect_keypoints'. */
+int gcs_detect_keypoints_grid(gcs_keypoint_grid_ctx* ctx, const gcs_keypoint_inputs* in,
+                              gcs_keypoint_grid_outputs* out);
+/* The same steps on the host (no device, no context): every pointer is a host array. */
+int gcs_detect_keypoints_grid_host(const gcs_keypoint_grid_config* cfg, const gcs_keypoint_inputs* in,
+                                   gcs_keypoint_grid_outputs* out);
+/* W_l, H_l, quota_l, n_cx, n_cy of every level for a width x height image, on the host; rows of levels
+ * >= n_levels are zero, and so are n_cx and n_cy of a level without cells. */
+int gcs_keypoint_grid_layout(const gcs_keypoint_grid_config* cfg, int32_t width, int32_t height,
+                             int32_t out[GCS_KEYPOINT_MAX_LEVELS][5]);
+
 /* ---------------------------------------------------------------- primitive path: map rendering */
 /* The reference's output side (backend/rendering.py, common/bev_pushforward.py) on the GPU, reading
  * an AtlasMapView's rows: for every (view, row) -- one thread per row, looping over the views -- the BEV pushforward to pixels, the 2 x 2 adjugate inverse,

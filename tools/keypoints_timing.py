@@ -15,9 +15,13 @@ each route after its own warm-up, the median of REPEAT calls:
   pyramid_detect    PyramidDetector.detect: the kernels and the 144-byte read-back of counts and level_counts
   extract_pyramid   VisualFeatureExtractor.extract(depth, rgb, None, K, keypoint_config=PyramidConfig()): pyramid
                     detector and feature operator chained
+  grid              the grid detector (GridDetector, cell_size 32, redistribute on) beside the pyramid detector on
+                    the same frame, 8 levels, at max_keypoints 4,096 and 512: `queue` (kernels alone) and `detect`
+                    of both, alternating, two rounds; the medians of both rounds and grid / pyramid of their means
 
---profile runs `detect` only and --profile-pyramid `pyramid_detect` only, WARMUP + REPEAT times, for a kernel trace
-taken from outside.  Prints one JSON line."""
+--profile runs `detect` only, --profile-pyramid `pyramid_detect` only and --profile-grid K the pyramid's and the
+grid's `detect` at max_keypoints K, WARMUP + REPEAT times, for a kernel trace taken from outside.  Prints one
+JSON line."""
 import argparse
 import json
 import os
@@ -44,6 +48,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--profile-pyramid", action="store_true")
+    ap.add_argument("--profile-grid", type=int, default=0, metavar="K")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -85,6 +90,15 @@ def main():
         print(json.dumps(dict(profile_calls=WARMUP + REPEAT)))
         return
 
+    if args.profile_grid:
+        p, g = KP.PyramidDetector(KP.PyramidConfig(max_keypoints=args.profile_grid)), \
+            KP.GridDetector(KP.GridConfig(max_keypoints=args.profile_grid))
+        for _ in range(WARMUP + REPEAT):
+            p.detect(rgb_d)
+            g.detect(rgb_d)
+        print(json.dumps(dict(profile_calls=WARMUP + REPEAT, max_keypoints=args.profile_grid)))
+        return
+
     pinned = torch.empty(4, dtype=torch.int32).pin_memory()
     counts_d = torch.zeros(4, dtype=torch.int32, device="cuda")
 
@@ -107,6 +121,24 @@ def main():
                      ("pyramid_detect", lambda: pyr.detect(rgb_d)),
                      ("extract_pyramid", lambda: ex.extract(depth_d, rgb_d, None, K, keypoint_config=pcfg))):
         out[name + "_ms"], out[name + "_ms_p10_p90"] = timed(fn)
+    for cap in (4096, 512):
+        p, g = KP.PyramidDetector(KP.PyramidConfig(max_keypoints=cap)), KP.GridDetector(KP.GridConfig(max_keypoints=cap))
+        pk, gk = p.detect(rgb_d), g.detect(rgb_d)
+        res = dict(pyramid_counts=list(pk.counts), grid_counts=list(gk.counts), grid_level_counts=[list(c) for c in gk.level_counts])
+        routes = (("pyramid_queue", lambda: p.queue(rgb_d)), ("grid_queue", lambda: g.queue(rgb_d)),
+                  ("pyramid_detect", lambda: p.detect(rgb_d)), ("grid_detect", lambda: g.detect(rgb_d)))
+        for name, _ in routes:
+            res[name + "_ms"], res[name + "_ms_p10_p90"] = [], []
+        for _ in range(2):
+            for name, fn in routes:
+                m, spread = timed(fn)
+                res[name + "_ms"].append(m)
+                res[name + "_ms_p10_p90"].append(spread)
+        for k in ("queue", "detect"):
+            res[k + "_ratio"] = sum(res[f"grid_{k}_ms"]) / sum(res[f"pyramid_{k}_ms"])
+        out[f"grid_k{cap}"] = res
+        p.close()
+        g.close()
     print(json.dumps(out))
     det.close()
     pyr.close()
