@@ -7,6 +7,7 @@ libgcslam_hip.so (include/gcslam_hip.h).  There is no CPU fallback.
 
 from . import _lib  # noqa: F401
 from . import keypoints  # noqa: F401
+from . import descriptors  # noqa: F401
 
 __version__ = "0.1.0"
 

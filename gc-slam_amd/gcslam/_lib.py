@@ -236,6 +236,36 @@ class GcsKeypointGridOutputs(C.Structure):   # level_counts: KEYPOINT_MAX_LEVELS
     _fields_ = [(n, C.c_void_p) for n in ("kp_u", "kp_v", "kp_response", "kp_level", "counts", "level_counts")]
 
 
+DESC_BYTES = 32
+MATCH_NONE = 257
+
+
+class GcsKeypointDescConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_levels", "scale_num", "scale_den", "max_width", "max_height",
+                                         "max_keypoints", "device")]
+
+
+class GcsKeypointDescKeypoints(C.Structure):   # kp_level may be null: every keypoint on level 0
+    _fields_ = [("n_keypoints", C.c_int32), ("kp_u", C.c_void_p), ("kp_v", C.c_void_p), ("kp_level", C.c_void_p)]
+
+
+class GcsKeypointDescOutputs(C.Structure):
+    _fields_ = [("kp_angle", C.c_void_p), ("kp_angle_bin", C.c_void_p), ("desc", C.c_void_p)]
+
+
+class GcsMatchConfig(C.Structure):
+    _fields_ = [("max_query", C.c_int32), ("max_train", C.c_int32), ("device", C.c_int32)]
+
+
+class GcsMatchInputs(C.Structure):   # q_bin and t_bin may be null: every row valid
+    _fields_ = [("n_query", C.c_int32), ("n_train", C.c_int32), ("q", C.c_void_p), ("t", C.c_void_p),
+                ("q_bin", C.c_void_p), ("t_bin", C.c_void_p)]
+
+
+class GcsMatchOutputs(C.Structure):
+    _fields_ = [("idx", C.c_void_p), ("dist", C.c_void_p), ("dist2", C.c_void_p)]
+
+
 class GcsRenderConfig(C.Structure):
     _fields_ = [("tile_size", C.c_int32), ("max_splats_per_tile", C.c_int32), ("fbm_octaves", C.c_int32),
                 ("fbm_gain", C.c_double), ("opacity_gamma", C.c_double), ("logdet0", C.c_double), ("eps", C.c_double),
@@ -523,6 +553,24 @@ _SIGS = [
     ("gcs_detect_keypoints_grid_host", C.c_int, [C.POINTER(GcsKeypointGridConfig), C.POINTER(GcsKeypointInputs),
                                                  C.POINTER(GcsKeypointGridOutputs)]),
     ("gcs_keypoint_grid_layout", C.c_int, [C.POINTER(GcsKeypointGridConfig), C.c_int32, C.c_int32, C.c_void_p]),
+    ("gcs_keypoint_desc_config_defaults", C.c_int, [C.POINTER(GcsKeypointDescConfig)]),
+    ("gcs_keypoint_desc_ctx_create", C.c_int, [C.POINTER(GcsKeypointDescConfig), C.POINTER(C.c_void_p)]),
+    ("gcs_keypoint_desc_ctx_destroy", C.c_int, [C.c_void_p]),
+    ("gcs_keypoint_desc_last_error", C.c_char_p, [C.c_void_p]),
+    ("gcs_keypoint_desc_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gcs_describe_keypoints", C.c_int, [C.c_void_p, C.POINTER(GcsKeypointInputs), C.POINTER(GcsKeypointDescKeypoints),
+                                         C.POINTER(GcsKeypointDescOutputs)]),
+    ("gcs_describe_keypoints_host", C.c_int, [C.POINTER(GcsKeypointDescConfig), C.POINTER(GcsKeypointInputs),
+                                              C.POINTER(GcsKeypointDescKeypoints), C.POINTER(GcsKeypointDescOutputs)]),
+    ("gcs_brief_pattern", C.c_int, [C.c_void_p]),
+    ("gcs_match_config_defaults", C.c_int, [C.POINTER(GcsMatchConfig)]),
+    ("gcs_match_ctx_create", C.c_int, [C.POINTER(GcsMatchConfig), C.POINTER(C.c_void_p)]),
+    ("gcs_match_ctx_destroy", C.c_int, [C.c_void_p]),
+    ("gcs_match_last_error", C.c_char_p, [C.c_void_p]),
+    ("gcs_match_ctx_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gcs_match_descriptors", C.c_int, [C.c_void_p, C.POINTER(GcsMatchInputs), C.POINTER(GcsMatchOutputs)]),
+    ("gcs_match_descriptors_host", C.c_int, [C.POINTER(GcsMatchConfig), C.POINTER(GcsMatchInputs),
+                                             C.POINTER(GcsMatchOutputs)]),
     ("gcs_render_config_defaults", C.c_int, [C.POINTER(GcsRenderConfig)]),
     ("gcs_render_ctx_create", C.c_int, [C.POINTER(GcsRenderConfig), C.POINTER(C.c_void_p)]),
     ("gcs_render_ctx_destroy", C.c_int, [C.c_void_p]),
@@ -589,7 +637,13 @@ _lib = None
 
 
 _AB_OPTIONAL = ("gcs_ctx_host_split", "gcs_ctx_worker_tid", "gcs_imu_odom_evidence_device",
-                "gcs_ctx_host_split_history")  # (round 6 entries)
+                "gcs_ctx_host_split_history",  # (round 6 entries)
+                # the describer and the matcher: absent from a build of before them (tools/keypoints_timing.py --grid-only)
+                "gcs_keypoint_desc_config_defaults", "gcs_keypoint_desc_ctx_create", "gcs_keypoint_desc_ctx_destroy",
+                "gcs_keypoint_desc_last_error", "gcs_keypoint_desc_ctx_set_stream", "gcs_describe_keypoints",
+                "gcs_describe_keypoints_host", "gcs_brief_pattern", "gcs_match_config_defaults", "gcs_match_ctx_create",
+                "gcs_match_ctx_destroy", "gcs_match_last_error", "gcs_match_ctx_set_stream", "gcs_match_descriptors",
+                "gcs_match_descriptors_host")
 
 
 def load():

@@ -2,9 +2,10 @@
 front of the FAST / ORB recipe at pyramid level 0 -- grey conversion, the FAST-9/16 segment test and score,
 strict 3 x 3 suppression, the border, the Harris response over a 7 x 7 block and the max_keypoints best by
 (response descending, raster index ascending), written in raster order.  This detector is the project's own.
-It follows the published FAST / ORB recipe, but it claims no parity with cv::ORB: there is no pyramid, there
-is no orientation, and there are no descriptors.  The definition is in include/gcslam_hip.h; the result is
-the (u, v, response) triple gcslam.visual takes as `keypoints`, device to device.
+It follows the published FAST / ORB recipe, but it claims no parity with cv::ORB: there is no pyramid here
+(PyramidDetector, below), and orientation and descriptors are gcslam.descriptors' own operators.  The definition
+is in include/gcslam_hip.h; the result is the (u, v, response) triple gcslam.visual takes as `keypoints`, device
+to device.
 
 PyramidDetector (gcs_detect_keypoints_pyramid) runs the same detector over a scale pyramid -- n_levels exact
 pixel-area resamples of the grey image at the rational scale scale_num / scale_den, a fixed quota of

@@ -702,8 +702,8 @@ int gcs_camera_splats_scan(gcs_camsplat_ctx* ctx, const gcs_camsplat_inputs* in,
  * by rank (element n / 2 of the sorted valid values, ties by lane) and the normal equations are
  * butterfly sums in a fixed order, so two calls agree bit for bit.  kp_u, kp_v, kp_response are
  * cv::KeyPoint's pt.x, pt.y, response: from any detector of the caller's, or from gcs_detect_keypoints
- * below, the library's own FAST-9 / Harris detector at pyramid level 0 (ORB's pyramid, orientation and
- * descriptors are not part of the library, and its detector claims no parity with cv::ORB).
+ * below, the library's own FAST-9 / Harris detector at pyramid level 0 (the pyramid, the orientation and the
+ * descriptors are entries of their own further below; none of them claims parity with cv::ORB).
  * Declared where the node leaves it open: with n_keypoints > max_features the max_features largest
  * responses are kept (ties to the lower index, NaN last) and written in input order; a keypoint with
  * a non-finite u or v, or |u| or |v| > 1e9, is outside the image; a NaN response weighs 0.  A keypoint
@@ -794,8 +794,8 @@ int gcs_visual_features_host(const gcs_visfeat_config* cfg, const gcs_visfeat_in
 /* ---------------------------------------------------------------- primitive path: keypoint detector */
 /* Keypoints from an 8-bit image on the GPU, in the form gcs_visfeat_inputs reads.  This detector is the
  * project's own.  It follows the published FAST / ORB recipe, but it claims no parity with cv::ORB: there
- * is no pyramid here (ORB's nlevels = 8, scaleFactor = 1.2: gcs_detect_keypoints_pyramid, below), there is no
- * orientation, and there are no descriptors.  Everything is exact integer arithmetic except the last step of the response:
+ * is no pyramid here (ORB's nlevels = 8, scaleFactor = 1.2: gcs_detect_keypoints_pyramid, below), and the
+ * orientation and the descriptors are operators of their own (gcs_describe_keypoints, further below).  Everything is exact integer arithmetic except the last step of the response:
  *  1. grey: gray8 as it is; rgb8 as g = (4899 R + 9617 G + 1868 B + 8192) >> 14.
  *  2. FAST-9/16 score: the ring is the radius-3 Bresenham circle, clockwise from the top: (0,-3) (1,-3)
  *     (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3).
@@ -861,7 +861,7 @@ int gcs_detect_keypoints_host(const gcs_keypoint_config* cfg, const gcs_keypoint
 
 /* Keypoints over a scale pyramid: the detector above on n_levels images, each level with its own share of
  * max_keypoints, every keypoint in level-0 pixel coordinates (what ORB's nlevels = 8, scaleFactor = 1.2 adds
- * to the detector front; still no orientation, no descriptors and no parity with cv::ORB).  The definition is
+ * to the detector front; orientation and descriptors: gcs_describe_keypoints; no parity with cv::ORB).  The definition is
  * the project's own and is integer-exact wherever the one above is.  With W x H the input, L = n_levels,
  * K = max_keypoints and the scale factor the rational scale_num / scale_den (no pow, no floating-point
  * scale anywhere):
@@ -995,6 +995,118 @@ int gcs_detect_keypoints_grid_host(const gcs_keypoint_grid_config* cfg, const gc
  * >= n_levels are zero, and so are n_cx and n_cy of a level without cells. */
 int gcs_keypoint_grid_layout(const gcs_keypoint_grid_config* cfg, int32_t width, int32_t height,
                              int32_t out[GCS_KEYPOINT_MAX_LEVELS][5]);
+
+/* ---------------------------------------------------------------- primitive path: keypoint descriptors */
+/* What ORB adds behind its detector -- an orientation per keypoint and a steered 256-bit BRIEF descriptor -- and
+ * a brute-force Hamming matcher to read the descriptors with.  The operators are the project's own: the angle
+ * bin, the 256 bits and every match output are defined in integer arithmetic, so device, host twin and a numpy
+ * restatement agree as bytes.  The pattern is a fixed pseudo-random one, not ORB's learned rBRIEF pattern, and
+ * no parity with cv::ORB is claimed.
+ *  D1. level and level pixel: keypoint i is (kp_u[i], kp_v[i]) in level-0 pixels on level kp_level[i]; a null
+ *      kp_level puts every keypoint on level 0 (gcs_detect_keypoints' rows).  With W_l x H_l = the level sizes
+ *      of P1 (n_levels, scale_num, scale_den from the config) and the level's grey image that of P2 -- the same
+ *      bytes the pyramid and grid detectors see -- the level pixel is x = floor((double(u) + 0.5) * W_l / W_0),
+ *      y likewise, every operation rounded on its own; this inverts P5's coordinate map exactly for every
+ *      keypoint a detector of this library emits.  A row is invalid when u or v is not finite, level is
+ *      outside [0, n_levels), the level has no pixels, or x < 16, x >= W_l - 16, y < 16 or y >= H_l - 16.  An
+ *      invalid row gets angle NaN, bin -1 and 32 zero bytes; the detectors' NaN / -1 padding rows are invalid,
+ *      and a detector with edge_threshold >= 16 emits no invalid row.
+ *  D2. moments: over the level pixels (dx, dy) with dx^2 + dy^2 <= 225 around (x, y), m10 = sum dx g,
+ *      m01 = sum dy g, exact in int32.
+ *  D3. angle bin: 32 bins of 11.25 degrees.  The direction table (C_k, S_k), k = 0..31, is scaled by 2^14:
+ *      (C_k, S_k) for k = 0..7 = (16384, 0), (16069, 3196), (15137, 6270), (13623, 9102), (11585, 11585),
+ *      (9102, 13623), (6270, 15137), (3196, 16069), i.e. round(2^14 cos) and round(2^14 sin) of 11.25 k degrees,
+ *      and C_{k+8} = -S_k, S_{k+8} = C_k, so a quarter turn of the table is exact.  The bin is the k that
+ *      maximises m10 C_k + m01 S_k in int64, ties to the lowest k; a flat patch has bin 0.
+ *  D4. angle: kp_angle = (float)atan2((double)m01, (double)m10) in radians (0 for m10 = m01 = 0).  It is
+ *      informative only: nothing is decided by it, and it may differ by one float32 ulp between builds.
+ *  D5. pattern: 256 pairs of int8 points (ax, ay, bx, by), a != b, |a|^2 and |b|^2 <= 169, produced by
+ *      tools/gen_brief_pattern.py (a stated 32-bit recurrence with a fixed seed, rejection-sampled on the disc)
+ *      and reported by gcs_brief_pattern.  For bin k the steered point of p = (x, y) is p_k = (rnd((x C_k -
+ *      y S_k) / 2^14), rnd((x S_k + y C_k) / 2^14)) with rnd rounding half away from zero, in integers; so
+ *      p_{k+8} is exactly p_k turned by a quarter turn.  The steering is computed, not tabulated.
+ *  D6. bits: B(p) is the 5 x 5 box sum of the level's grey image centred at (x, y) + p (at most 6375).  Bit i is
+ *      1 when B(a_k,i) < B(b_k,i); it is stored in byte i / 8 at bit i % 8 of the keypoint's 32-byte row.  The
+ *      reach is 14 + 2 = 16 level pixels, the margin of D1.
+ *  D7. match: q is n_query x 32 bytes, t is n_train x 32 bytes, both 4-byte aligned; q_bin and t_bin are
+ *      optional int32 arrays (kp_angle_bin of the describer): a row is valid when its value is >= 0, and a null
+ *      array makes every row valid.  For every query row: idx = the valid train row of least Hamming distance,
+ *      ties to the lowest index, -1 when there is none or the query is invalid; dist = that distance, 257 when
+ *      idx is -1; dist2 = the least distance among the other valid train rows, 257 when there is none or the
+ *      query is invalid.  All int32.  n_query = 0 and n_train = 0 are legal.  No floating point and no atomics
+ *      are involved: the result is bitwise repeatable.
+ * gcs_describe_keypoints queues two kernels whatever n_levels is (the packed resample of P2, then one wave per
+ * keypoint) and makes no host synchronisation; the row count is the caller's n_keypoints, so it chains behind a
+ * detector with n_keypoints = max_keypoints and the padding.  gcs_match_descriptors queues at most two kernels.
+ * Calls on one context must be serialised. */
+typedef struct gcs_keypoint_desc_ctx gcs_keypoint_desc_ctx;
+typedef struct gcs_match_ctx gcs_match_ctx;
+#define GCS_DESC_BYTES 32
+#define GCS_MATCH_NONE 257
+
+typedef struct {
+  int32_t n_levels;              /* 8, as gcs_keypoint_pyramid_config's, same ranges */
+  int32_t scale_num, scale_den;  /* 6, 5 */
+  int32_t max_width, max_height; /* 1920 x 1080: capacity of the packed workspace */
+  int32_t max_keypoints;         /* 4096; 1 .. 65536: the largest n_keypoints of a call */
+  int32_t device;
+} gcs_keypoint_desc_config;
+
+/* The keypoints of one call: device pointers for gcs_describe_keypoints, host pointers for the host twin. */
+typedef struct {
+  int32_t n_keypoints;           /* 0 .. max_keypoints */
+  const float *kp_u, *kp_v;      /* n_keypoints each, level-0 pixels */
+  const int32_t* kp_level;       /* n_keypoints, or null: every keypoint on level 0 */
+} gcs_keypoint_desc_keypoints;
+
+typedef struct {
+  float* kp_angle;               /* n_keypoints, radians (D4); NaN on an invalid row */
+  int32_t* kp_angle_bin;         /* n_keypoints, 0 .. 31 (D3); -1 on an invalid row */
+  uint8_t* desc;                 /* n_keypoints x 32 (D6); zero on an invalid row */
+} gcs_keypoint_desc_outputs;
+
+int gcs_keypoint_desc_config_defaults(gcs_keypoint_desc_config* cfg);
+/* GCS_ERR_ARG, before any device call, for a config outside the ranges above. */
+int gcs_keypoint_desc_ctx_create(const gcs_keypoint_desc_config* cfg, gcs_keypoint_desc_ctx** out);
+int gcs_keypoint_desc_ctx_destroy(gcs_keypoint_desc_ctx* ctx);
+const char* gcs_keypoint_desc_last_error(const gcs_keypoint_desc_ctx* ctx);
+int gcs_keypoint_desc_ctx_set_stream(gcs_keypoint_desc_ctx* ctx, void* stream);
+/* Queues its kernels on the context's stream and returns.  GCS_ERR_ARG (last_error set) for an image as
+ * gcs_detect_keypoints refuses it, n_keypoints outside [0, max_keypoints] or, with n_keypoints > 0, a null array
+ * other than kp_level. */
+int gcs_describe_keypoints(gcs_keypoint_desc_ctx* ctx, const gcs_keypoint_inputs* in,
+                           const gcs_keypoint_desc_keypoints* kps, gcs_keypoint_desc_outputs* out);
+/* The same steps on the host (no device, no context): every pointer is a host array. */
+int gcs_describe_keypoints_host(const gcs_keypoint_desc_config* cfg, const gcs_keypoint_inputs* in,
+                                const gcs_keypoint_desc_keypoints* kps, gcs_keypoint_desc_outputs* out);
+/* The pattern of D5: 256 rows of ax, ay, bx, by. */
+int gcs_brief_pattern(int8_t out[256][4]);
+
+typedef struct {
+  int32_t max_query, max_train;  /* 4096 each; 1 .. 1048576: the largest n_query and n_train of a call */
+  int32_t device;
+} gcs_match_config;
+
+typedef struct {
+  int32_t n_query, n_train;
+  const uint8_t *q, *t;          /* n_query x 32 and n_train x 32 bytes, 4-byte aligned */
+  const int32_t *q_bin, *t_bin;  /* n_query and n_train, or null (D7) */
+} gcs_match_inputs;
+
+typedef struct {
+  int32_t *idx, *dist, *dist2;   /* n_query each (D7) */
+} gcs_match_outputs;
+
+int gcs_match_config_defaults(gcs_match_config* cfg);
+int gcs_match_ctx_create(const gcs_match_config* cfg, gcs_match_ctx** out);
+int gcs_match_ctx_destroy(gcs_match_ctx* ctx);
+const char* gcs_match_last_error(const gcs_match_ctx* ctx);
+int gcs_match_ctx_set_stream(gcs_match_ctx* ctx, void* stream);
+/* Queues its kernels on the context's stream and returns.  GCS_ERR_ARG (last_error set) for a count below 0 or
+ * above the context's capacity, a null or misaligned array that the counts make necessary. */
+int gcs_match_descriptors(gcs_match_ctx* ctx, const gcs_match_inputs* in, gcs_match_outputs* out);
+/* The same on the host; of the config only the capacities are looked at. */
+int gcs_match_descriptors_host(const gcs_match_config* cfg, const gcs_match_inputs* in, gcs_match_outputs* out);
 
 /* ---------------------------------------------------------------- primitive path: map rendering */
 /* The reference's output side (backend/rendering.py, common/bev_pushforward.py) on the GPU, reading

@@ -18,6 +18,16 @@ each route after its own warm-up, the median of REPEAT calls:
   grid              the grid detector (GridDetector, cell_size 32, redistribute on) beside the pyramid detector on
                     the same frame, 8 levels, at max_keypoints 4,096 and 512: `queue` (kernels alone) and `detect`
                     of both, alternating, two rounds; the medians of both rounds and grid / pyramid of their means
+  describe          gcslam.descriptors.KeypointDescriber.queue on the grid detector's keypoints of the frame at
+                    max_keypoints 512 and 4,096 (orientation and 256-bit descriptor; nothing is waited for inside the
+                    timed call), and `describe_keypoints`, the cached route
+  match             DescriptorMatcher.queue of the frame's descriptors against those of the frame moved by (5, 3)
+                    pixels, 512 x 512 and 4,096 x 4,096 (nearest and second nearest of every row, one way), and
+                    `match_descriptors` with its defaults (both ways, the filters and the result's length read back)
+
+--desc prints the describe and match lines and GridDetector's `queue` and `detect` at both sizes only; --grid-only the
+GridDetector lines only (with GCSLAM_LIB naming a build of before the describer, for a same-session comparison).
+--profile-desc K runs the describer's and the matcher's `queue` at max_keypoints K for a kernel trace.
 
 --profile runs `detect` only, --profile-pyramid `pyramid_detect` only and --profile-grid K the pyramid's and the
 grid's `detect` at max_keypoints K, WARMUP + REPEAT times, for a kernel trace taken from outside.  Prints one
@@ -49,6 +59,9 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--profile-pyramid", action="store_true")
     ap.add_argument("--profile-grid", type=int, default=0, metavar="K")
+    ap.add_argument("--desc", action="store_true")
+    ap.add_argument("--grid-only", action="store_true")
+    ap.add_argument("--profile-desc", type=int, default=0, metavar="K")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -99,6 +112,50 @@ def main():
         print(json.dumps(dict(profile_calls=WARMUP + REPEAT, max_keypoints=args.profile_grid)))
         return
 
+    def desc_lines(caps, grid_only=False, profile=False):
+        """The describe and match lines (and GridDetector's own) at every cap."""
+        res = {}
+        moved = torch.roll(rgb_d, (3, 5), (0, 1)).contiguous()
+        for cap in caps:
+            g = KP.GridDetector(KP.GridConfig(max_keypoints=cap))
+            ka, kb = g.detect(rgb_d), g.detect(moved)
+            r = dict(grid_counts=list(ka.counts), moved_counts=list(kb.counts))
+            routes = [("grid_queue", lambda: g.queue(rgb_d)), ("grid_detect", lambda: g.detect(rgb_d))]
+            if not grid_only:
+                from gcslam import descriptors as D
+                d = D.KeypointDescriber(D.DescriptorConfig(max_keypoints=cap))
+                m = D.DescriptorMatcher(D.MatchConfig(cap, cap))
+                da, db = d.describe(rgb_d, ka), d.describe(moved, kb)
+                pairs = D.match_descriptors(da, db)
+                r.update(valid=int((da.angle_bin >= 0).sum()), pairs=int(pairs[0].shape[0]))
+                routes = [("describe_queue", lambda: d.queue(rgb_d, ka[0], ka[1], ka.level)),
+                          ("describe_keypoints", lambda: D.describe_keypoints(rgb_d, ka, D.DescriptorConfig(max_keypoints=cap))),
+                          ("match_queue", lambda: m.queue(da.desc, db.desc, da.angle_bin, db.angle_bin)),
+                          ("match_descriptors", lambda: D.match_descriptors(da, db))] + routes
+            if profile:
+                for _ in range(WARMUP + REPEAT):
+                    routes[0][1]()
+                    routes[2][1]()
+                torch.cuda.synchronize()
+            else:
+                for name, _ in routes:
+                    r[name + "_ms"], r[name + "_ms_p10_p90"] = [], []
+                for _ in range(2):
+                    for name, fn in routes:
+                        med, spread = timed(fn)
+                        r[name + "_ms"].append(med)
+                        r[name + "_ms_p10_p90"].append(spread)
+            res[f"k{cap}"] = r
+            g.close()
+        return res
+
+    if args.desc or args.grid_only or args.profile_desc:
+        caps = (args.profile_desc,) if args.profile_desc else (512, 4096)
+        out = dict(width=W, height=H, warmup=WARMUP, repeat=REPEAT, lib=os.environ.get("GCSLAM_LIB", "in-tree"))
+        out.update(desc_lines(caps, args.grid_only, bool(args.profile_desc)))
+        print(json.dumps(out))
+        return
+
     pinned = torch.empty(4, dtype=torch.int32).pin_memory()
     counts_d = torch.zeros(4, dtype=torch.int32, device="cuda")
 
@@ -139,6 +196,7 @@ def main():
         out[f"grid_k{cap}"] = res
         p.close()
         g.close()
+    out["desc"] = desc_lines((512, 4096))
     print(json.dumps(out))
     det.close()
     pyr.close()
