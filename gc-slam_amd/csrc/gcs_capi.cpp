@@ -1208,6 +1208,9 @@ int gcs_ctx_create(const gcs_config* cfg, gcs_ctx** out) {
   // scan's bin kernel had written -- run-to-run differences of the zero bins' Sigma, tools/
   // determinism_check.py at C3).  Drain the null stream first.
   if (bad(hipStreamSynchronize(nullptr))) return GCS_ERR_HIP;
+  // launch_map_derive reports hipGetLastError(), which also holds what an earlier, unrelated call of this thread
+  // left there (another context's create refused for a device that does not exist, say): drop that first
+  (void)hipGetLastError();
   if (bad(launch_map_derive(c->d_map, c->d_derived, c->B, c->d_partials, c->d_scalars, c->d_touched,
                             c->stream)))
     return GCS_ERR_HIP;

@@ -107,4 +107,26 @@ GCS_HD void kd_match_step(int d, int j, int* dist, int* idx, int* dist2) {
   }
 }
 
+// D8: the levels within max_level_diff of level ql, as int32 bounds: for an int32 level tl, lo <= tl <= hi is
+// |tl - ql| <= max_level_diff in exact integers (bounds beyond int32 saturate, which no int32 level can tell apart).
+GCS_HD void kd_level_window(int32_t ql, int32_t max_level_diff, int32_t* lo, int32_t* hi) {
+  const int64_t a = (int64_t)ql - max_level_diff, b = (int64_t)ql + max_level_diff;
+  *lo = (int32_t)(a < INT32_MIN ? INT32_MIN : a);
+  *hi = (int32_t)(b > INT32_MAX ? INT32_MAX : b);
+}
+
+// D8: position (tu, tv) on level tl lies in the window of radius `radius` around (pu, pv) and of levels lo .. hi.
+// Each difference is one float32 subtraction (|a - b| = |b - a| exactly, and so is the level test symmetric, so
+// either row may be the query); a NaN or an inf - inf fails its comparison.
+GCS_HD bool kd_gate(float tu, float tv, int32_t tl, float pu, float pv, int32_t lo, int32_t hi, float radius) {
+  const float du = tu - pu, dv = tv - pv;
+  return (int)(fabsf(du) <= radius) & (int)(fabsf(dv) <= radius) & (int)(tl >= lo) & (int)(tl <= hi);
+}
+
+// D9: the filters of one query row on its merged (idx, dist, dist2); the cross check is the caller's
+GCS_HD bool kd_pair_filters(int idx, int dist, int dist2, int max_distance, int ratio_num, int ratio_den) {
+  if (idx < 0 || dist > max_distance) return false;
+  return ratio_den == 0 || (int64_t)dist * ratio_den < (int64_t)ratio_num * dist2;
+}
+
 }  // namespace gcs

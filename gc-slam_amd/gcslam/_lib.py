@@ -266,6 +266,24 @@ class GcsMatchOutputs(C.Structure):
     _fields_ = [("idx", C.c_void_p), ("dist", C.c_void_p), ("dist2", C.c_void_p)]
 
 
+class GcsMatchGate(C.Structure):   # the levels and the prediction may be null (D8)
+    _fields_ = [("q_u", C.c_void_p), ("q_v", C.c_void_p), ("q_level", C.c_void_p), ("t_u", C.c_void_p), ("t_v", C.c_void_p),
+                ("t_level", C.c_void_p), ("q_pu", C.c_void_p), ("q_pv", C.c_void_p), ("radius", C.c_float),
+                ("max_level_diff", C.c_int32)]
+
+
+class GcsMatchGatedOutputs(C.Structure):   # n_cand may be null
+    _fields_ = [("idx", C.c_void_p), ("dist", C.c_void_p), ("dist2", C.c_void_p), ("n_cand", C.c_void_p)]
+
+
+class GcsMatchFilter(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("max_distance", "ratio_num", "ratio_den", "cross_check")]
+
+
+class GcsMatchPairOutputs(C.Structure):
+    _fields_ = [("pair_a", C.c_void_p), ("pair_b", C.c_void_p), ("pair_dist", C.c_void_p), ("count", C.c_void_p)]
+
+
 class GcsRenderConfig(C.Structure):
     _fields_ = [("tile_size", C.c_int32), ("max_splats_per_tile", C.c_int32), ("fbm_octaves", C.c_int32),
                 ("fbm_gain", C.c_double), ("opacity_gamma", C.c_double), ("logdet0", C.c_double), ("eps", C.c_double),
@@ -571,6 +589,16 @@ _SIGS = [
     ("gcs_match_descriptors", C.c_int, [C.c_void_p, C.POINTER(GcsMatchInputs), C.POINTER(GcsMatchOutputs)]),
     ("gcs_match_descriptors_host", C.c_int, [C.POINTER(GcsMatchConfig), C.POINTER(GcsMatchInputs),
                                              C.POINTER(GcsMatchOutputs)]),
+    ("gcs_match_gate_defaults", C.c_int, [C.POINTER(GcsMatchGate)]),
+    ("gcs_match_filter_defaults", C.c_int, [C.POINTER(GcsMatchFilter)]),
+    ("gcs_match_descriptors_gated", C.c_int, [C.c_void_p, C.POINTER(GcsMatchInputs), C.POINTER(GcsMatchGate),
+                                              C.POINTER(GcsMatchGatedOutputs)]),
+    ("gcs_match_pairs", C.c_int, [C.c_void_p, C.POINTER(GcsMatchInputs), C.POINTER(GcsMatchGate), C.POINTER(GcsMatchFilter),
+                                  C.POINTER(GcsMatchPairOutputs)]),
+    ("gcs_match_descriptors_gated_host", C.c_int, [C.POINTER(GcsMatchConfig), C.POINTER(GcsMatchInputs),
+                                                   C.POINTER(GcsMatchGate), C.POINTER(GcsMatchGatedOutputs)]),
+    ("gcs_match_pairs_host", C.c_int, [C.POINTER(GcsMatchConfig), C.POINTER(GcsMatchInputs), C.POINTER(GcsMatchGate),
+                                       C.POINTER(GcsMatchFilter), C.POINTER(GcsMatchPairOutputs)]),
     ("gcs_render_config_defaults", C.c_int, [C.POINTER(GcsRenderConfig)]),
     ("gcs_render_ctx_create", C.c_int, [C.POINTER(GcsRenderConfig), C.POINTER(C.c_void_p)]),
     ("gcs_render_ctx_destroy", C.c_int, [C.c_void_p]),
@@ -643,7 +671,10 @@ _AB_OPTIONAL = ("gcs_ctx_host_split", "gcs_ctx_worker_tid", "gcs_imu_odom_eviden
                 "gcs_keypoint_desc_last_error", "gcs_keypoint_desc_ctx_set_stream", "gcs_describe_keypoints",
                 "gcs_describe_keypoints_host", "gcs_brief_pattern", "gcs_match_config_defaults", "gcs_match_ctx_create",
                 "gcs_match_ctx_destroy", "gcs_match_last_error", "gcs_match_ctx_set_stream", "gcs_match_descriptors",
-                "gcs_match_descriptors_host")
+                "gcs_match_descriptors_host",
+                # the gate and the pairs: absent from a build of before them (tools/keypoints_timing.py --no-gate)
+                "gcs_match_gate_defaults", "gcs_match_filter_defaults", "gcs_match_descriptors_gated", "gcs_match_pairs",
+                "gcs_match_descriptors_gated_host", "gcs_match_pairs_host")
 
 
 def load():

@@ -6,6 +6,11 @@ in include/gcslam_hip.h).  The test pattern is a fixed pseudo-random one (tools/
 learned rBRIEF pattern, and no parity with cv::ORB is claimed.  The angle bin, the 256 bits and every match output
 are integer arithmetic: device, host twin and tests/keypoints_desc_ref.py agree as bytes.
 
+gcs_match_descriptors_gated and gcs_match_pairs (D8, D9) match inside a search window and build the pairs on the
+device: DescriptorMatcher.queue_gated and queue_pairs wait for nothing, match_pairs makes one wait for the 4-byte
+count, and nearest_gated_host, pairs_host and match_pairs_host are the host twins; tests/keypoints_gate_ref.py is
+their restatement.  match_descriptors is the earlier route, left as it was.
+
 The describer's n_levels, scale_num and scale_den must be those of the detector whose keypoints it is given: they
 decide the level images.  A single-level detector's result (no .level) is described on level 0."""
 
@@ -236,6 +241,41 @@ def match_config_struct(config: Optional[MatchConfig] = None, device: int = 0) -
     return c
 
 
+@dataclass(frozen=True)
+class GateConfig:
+    """D8's window: radius in level-0 pixels around the predicted position, and the most levels apart."""
+    radius: float = 16.0
+    max_level_diff: int = 1
+
+
+def gate_defaults() -> GateConfig:
+    """gcs_match_gate_defaults as a GateConfig."""
+    g = L.GcsMatchGate()
+    L.check(L.load().gcs_match_gate_defaults(C.byref(g)), None, "gcs_match_gate_defaults")
+    return GateConfig(float(g.radius), int(g.max_level_diff))
+
+
+def filter_defaults():
+    """gcs_match_filter_defaults: (max_distance, (ratio_num, ratio_den), cross_check)."""
+    f = L.GcsMatchFilter()
+    L.check(L.load().gcs_match_filter_defaults(C.byref(f)), None, "gcs_match_filter_defaults")
+    return int(f.max_distance), (int(f.ratio_num), int(f.ratio_den)), bool(f.cross_check)
+
+
+def _gate_struct(gate: GateConfig, pointers) -> "L.GcsMatchGate":
+    """gcs_match_gate of q_u, q_v, q_level, t_u, t_v, t_level, q_pu, q_pv (addresses or None) and a GateConfig."""
+    return L.GcsMatchGate(*pointers, float(gate.radius), int(gate.max_level_diff))
+
+
+def _filter_struct(max_distance, ratio, cross_check) -> "L.GcsMatchFilter":
+    """gcs_match_filter of match_descriptors' arguments: None switches a filter off (D9)."""
+    num, den = (4, 0) if ratio is None else (int(r) for r in ratio)
+    if ratio is not None and den == 0:
+        raise ValueError("ratio: a denominator of 0")
+    far = 256 if max_distance is None else max(-1, min(256, int(max_distance)))   # (no distance is below 0 or above 256)
+    return L.GcsMatchFilter(far, num, den, 1 if cross_check else 0)
+
+
 def _sides(a):
     """(desc, angle_bin or None) of a Descriptors object or of a bare (n, 32) uint8 array."""
     if isinstance(a, Descriptors):
@@ -309,6 +349,75 @@ class DescriptorMatcher:
                   "gcs_match_ctx_set_stream")
         self._chk(self.lib.gcs_match_descriptors(self.h, C.byref(i), C.byref(o)), "gcs_match_descriptors")
         return out[0], out[1], out[2]
+
+    def _positions(self, kp, n, what):
+        """(u, v, level or None) of one side as device tensors of n rows."""
+        import torch
+        u, v, level = _keypoint_arrays(kp)
+        return (KeypointDescriber._rows(self, u, torch.float32, n, what + " u"),
+                KeypointDescriber._rows(self, v, torch.float32, n, what + " v"),
+                None if level is None else KeypointDescriber._rows(self, level, torch.int32, n, what + " level"))
+
+    def _gate(self, kp_q, kp_t, predicted, gate, n_q, n_t):
+        """(gcs_match_gate, the tensors it points into) of device positions."""
+        import torch
+        gate = gate or GateConfig()
+        q, t = self._positions(kp_q, n_q, "kp_q"), self._positions(kp_t, n_t, "kp_t")
+        p = (None, None)
+        if predicted is not None:
+            pu, pv = tuple(predicted)[:2]
+            p = (KeypointDescriber._rows(self, pu, torch.float32, n_q, "predicted u"),
+                 KeypointDescriber._rows(self, pv, torch.float32, n_q, "predicted v"))
+        g = _gate_struct(gate, [None if x is None or not x.shape[0] else x.data_ptr() for x in q + t + p])
+        return g, (q, t, p)
+
+    def _inputs(self, q, t, q_bin, t_bin):
+        q, t = self._desc(q, "q"), self._desc(t, "t")
+        n_q, n_t = int(q.shape[0]), int(t.shape[0])
+        q_bin, t_bin = self._bins(q_bin, n_q, "q_bin"), self._bins(t_bin, n_t, "t_bin")
+        i = L.GcsMatchInputs(n_q, n_t, q.data_ptr() if n_q else None, t.data_ptr() if n_t else None,
+                             None if q_bin is None or not n_q else q_bin.data_ptr(),
+                             None if t_bin is None or not n_t else t_bin.data_ptr())
+        return i, n_q, n_t, (q, t, q_bin, t_bin)
+
+    def queue_gated(self, q, t, kp_q, kp_t, predicted=None, gate: Optional["GateConfig"] = None, q_bin=None, t_bin=None):
+        """gcs_match_descriptors_gated on the current torch stream, without waiting: (idx, dist, dist2, n_cand), int32
+        device tensors of one entry per query row (D8).  kp_q, kp_t: a detector's result or a (u, v[, response[,
+        level]]) tuple; predicted: (pu, pv) of every query row, or None (the query's own position); gate: a
+        GateConfig (None: its defaults)."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        i, n_q, n_t, keep = self._inputs(q, t, q_bin, t_bin)
+        g, keep_g = self._gate(kp_q, kp_t, predicted, gate, n_q, n_t)
+        out = torch.empty((4, n_q), dtype=torch.int32, device=dev)
+        o = L.GcsMatchGatedOutputs(*((out[j].data_ptr() if n_q else None) for j in range(4)))
+        self._chk(self.lib.gcs_match_ctx_set_stream(self.h, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  "gcs_match_ctx_set_stream")
+        self._chk(self.lib.gcs_match_descriptors_gated(self.h, C.byref(i), C.byref(g), C.byref(o)), "gcs_match_descriptors_gated")
+        return out[0], out[1], out[2], out[3]
+
+    def queue_pairs(self, q, t, kp_q=None, kp_t=None, predicted=None, gate: Optional["GateConfig"] = None, q_bin=None,
+                    t_bin=None, max_distance: Optional[int] = 64, ratio=(4, 5), cross_check: bool = True):
+        """gcs_match_pairs on the current torch stream, without waiting: the padded (pair_a, pair_b, pair_dist) of
+        n_query entries each and count, a one-entry tensor, all int32 on the device (D9).  Without kp_q and kp_t
+        there is no gate."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        i, n_q, n_t, keep = self._inputs(q, t, q_bin, t_bin)
+        g = None
+        if kp_q is not None or kp_t is not None or gate is not None:
+            if kp_q is None or kp_t is None:
+                raise ValueError("a gate needs both kp_q and kp_t")
+            g, keep_g = self._gate(kp_q, kp_t, predicted, gate, n_q, n_t)
+        f = _filter_struct(max_distance, ratio, cross_check)
+        out = torch.empty((3, n_q), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        o = L.GcsMatchPairOutputs(*((out[j].data_ptr() if n_q else None) for j in range(3)), count.data_ptr())
+        self._chk(self.lib.gcs_match_ctx_set_stream(self.h, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  "gcs_match_ctx_set_stream")
+        self._chk(self.lib.gcs_match_pairs(self.h, C.byref(i), None if g is None else C.byref(g), C.byref(f), C.byref(o)),
+                  "gcs_match_pairs")
+        return out[0], out[1], out[2], count
 
 
 _matchers = {}
@@ -395,3 +504,98 @@ def match_descriptors_host(a, b, max_distance: Optional[int] = 64, ratio=(4, 5),
         keep = keep & (back[np.clip(idx, 0, None)] == np.arange(len(idx))) if len(back) else keep & False
     at = np.nonzero(keep)[0]
     return at.astype(np.int32), idx[at], dist[at]
+
+
+# ---- the gate and the pairs (D8, D9)
+
+def match_pairs(a, b, kp_a=None, kp_b=None, predicted=None, gate: Optional[GateConfig] = None,
+                max_distance: Optional[int] = 64, ratio=(4, 5), cross_check: bool = True, device: int = 0):
+    """match_descriptors' triple (idx_a, idx_b, dist) through gcs_match_pairs: both searches, the filters, the cross
+    check and the compaction in one device pass, cut to the count -- one wait, for its 4 bytes.  With kp_a and kp_b
+    (detector results or (u, v[, response[, level]]) tuples) a row of b is a candidate only inside the window of
+    `gate` (None: GateConfig()) around `predicted` = (pu, pv), where each row of a is expected in b's image (None:
+    the row's own position).  Passing gate without both kp_a and kp_b raises ValueError."""
+    import torch
+    if (gate is not None or predicted is not None) and (kp_a is None or kp_b is None):
+        raise ValueError("a gate needs both kp_a and kp_b")
+    qa, ba = _sides(a)
+    qb, bb = _sides(b)
+    m = _matcher_for(device, int(qa.shape[0]), int(qb.shape[0]))
+    pa, pb, pd, count = m.queue_pairs(qa, qb, kp_a, kp_b, predicted, gate, ba, bb, max_distance, ratio, cross_check)
+    n = int(count.item())
+    return pa[:n], pb[:n], pd[:n]
+
+
+def _host_inputs(q, t, q_bin, t_bin):
+    q, t = np.ascontiguousarray(q, np.uint8), np.ascontiguousarray(t, np.uint8)
+    for x, what in ((q, "q"), (t, "t")):
+        if x.ndim != 2 or x.shape[1] != DESC_BYTES:
+            raise ValueError(f"{what}: {x.shape}, expected (n, 32) uint8")
+    n_q, n_t = q.shape[0], t.shape[0]
+    q_bin = None if q_bin is None else np.ascontiguousarray(q_bin, np.int32)
+    t_bin = None if t_bin is None else np.ascontiguousarray(t_bin, np.int32)
+    if (q_bin is not None and q_bin.shape != (n_q,)) or (t_bin is not None and t_bin.shape != (n_t,)):
+        raise ValueError("q_bin, t_bin: one entry per row")
+    i = L.GcsMatchInputs(n_q, n_t, q.ctypes.data if n_q else None, t.ctypes.data if n_t else None,
+                         None if q_bin is None or not n_q else q_bin.ctypes.data,
+                         None if t_bin is None or not n_t else t_bin.ctypes.data)
+    return i, n_q, n_t, (q, t, q_bin, t_bin)
+
+
+def _host_gate(kp_q, kp_t, predicted, gate, n_q, n_t):
+    rows = []
+    for kp, n in ((kp_q, n_q), (kp_t, n_t)):
+        u, v, level = _keypoint_arrays(kp)
+        rows += [np.ascontiguousarray(u, np.float32), np.ascontiguousarray(v, np.float32),
+                 None if level is None else np.ascontiguousarray(level, np.int32)]
+        if any(x is not None and x.shape != (n,) for x in rows[-3:]):
+            raise ValueError("keypoints: u, v and level of one entry per descriptor row")
+    if predicted is None:
+        rows += [None, None]
+    else:
+        rows += [np.ascontiguousarray(x, np.float32) for x in tuple(predicted)[:2]]
+        if any(x.shape != (n_q,) for x in rows[-2:]):
+            raise ValueError("predicted: (pu, pv) of one entry per query row")
+    return _gate_struct(gate or GateConfig(), [None if x is None or not x.shape[0] else x.ctypes.data for x in rows]), rows
+
+
+def nearest_gated_host(q, t, kp_q, kp_t, predicted=None, gate: Optional[GateConfig] = None, q_bin=None, t_bin=None):
+    """gcs_match_descriptors_gated_host: (idx, dist, dist2, n_cand) int32 numpy arrays of one entry per row of q (D8)."""
+    i, n_q, n_t, keep = _host_inputs(q, t, q_bin, t_bin)
+    g, keep_g = _host_gate(kp_q, kp_t, predicted, gate, n_q, n_t)
+    c = match_config_struct(MatchConfig(max(n_q, 1), max(n_t, 1)), 0)
+    out = np.empty((4, n_q), np.int32)
+    o = L.GcsMatchGatedOutputs(*((out[j].ctypes.data if n_q else None) for j in range(4)))
+    rc = L.load().gcs_match_descriptors_gated_host(C.byref(c), C.byref(i), C.byref(g), C.byref(o))
+    if rc != 0:
+        raise ValueError(f"gcs_match_descriptors_gated_host failed ({rc})")
+    return out[0], out[1], out[2], out[3]
+
+
+def pairs_host(q, t, kp_q=None, kp_t=None, predicted=None, gate: Optional[GateConfig] = None, q_bin=None, t_bin=None,
+               max_distance: Optional[int] = 64, ratio=(4, 5), cross_check: bool = True):
+    """gcs_match_pairs_host: the padded (pair_a, pair_b, pair_dist) and the count, as DescriptorMatcher.queue_pairs."""
+    i, n_q, n_t, keep = _host_inputs(q, t, q_bin, t_bin)
+    g = None
+    if kp_q is not None or kp_t is not None or gate is not None or predicted is not None:
+        if kp_q is None or kp_t is None:
+            raise ValueError("a gate needs both kp_q and kp_t")
+        g, keep_g = _host_gate(kp_q, kp_t, predicted, gate, n_q, n_t)
+    f = _filter_struct(max_distance, ratio, cross_check)
+    c = match_config_struct(MatchConfig(max(n_q, 1), max(n_t, 1)), 0)
+    out, count = np.empty((3, n_q), np.int32), np.full(1, -7, np.int32)
+    o = L.GcsMatchPairOutputs(*((out[j].ctypes.data if n_q else None) for j in range(3)), count.ctypes.data)
+    rc = L.load().gcs_match_pairs_host(C.byref(c), C.byref(i), None if g is None else C.byref(g), C.byref(f), C.byref(o))
+    if rc != 0:
+        raise ValueError(f"gcs_match_pairs_host failed ({rc})")
+    return out[0], out[1], out[2], count
+
+
+def match_pairs_host(a, b, kp_a=None, kp_b=None, predicted=None, gate: Optional[GateConfig] = None,
+                     max_distance: Optional[int] = 64, ratio=(4, 5), cross_check: bool = True):
+    """match_pairs through gcs_match_pairs_host: numpy in and out, no device."""
+    qa, ba = _sides(a)
+    qb, bb = _sides(b)
+    pa, pb, pd, count = pairs_host(qa, qb, kp_a, kp_b, predicted, gate, ba, bb, max_distance, ratio, cross_check)
+    n = int(count[0])
+    return pa[:n], pb[:n], pd[:n]

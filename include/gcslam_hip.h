@@ -1035,10 +1035,31 @@ int gcs_keypoint_grid_layout(const gcs_keypoint_grid_config* cfg, int32_t width,
  *      idx is -1; dist2 = the least distance among the other valid train rows, 257 when there is none or the
  *      query is invalid.  All int32.  n_query = 0 and n_train = 0 are legal.  No floating point and no atomics
  *      are involved: the result is bitwise repeatable.
+ *  D8. gate: optional per-row positions q_u, q_v, t_u, t_v (float32, level-0 pixels, as the detectors emit) and
+ *      levels q_level, t_level (int32; a null level array puts every row on level 0).  The prediction q_pu, q_pv
+ *      (float32) is where query row i is expected in the train image; a null prediction uses q_u, q_v.  With
+ *      radius (float32, finite, >= 0) and max_level_diff (int32, >= 0), train row j is a candidate of query row
+ *      i -- C(i, j) -- when both rows are valid in D7's sense, fabsf(t_u[j] - q_pu[i]) <= radius, the same for
+ *      v, and |t_level[j] - q_level[i]| <= max_level_diff (in exact integers).  Each difference is one IEEE
+ *      float32 subtraction, never contracted; a non-finite position or prediction makes every comparison false,
+ *      so that row has no candidates.  Per query row idx, dist, dist2 are D7's taken over the candidates only --
+ *      the minimum is over (distance, index), so ties go to the lowest index whatever order rows are visited in
+ *      -- and -1 / 257 / 257 where there are none; n_cand is the number of candidates (int32).  C is defined
+ *      once, from the query side: the backward search of train row j is over the query rows i with C(i, j), by
+ *      (distance, lowest i), which makes the cross check symmetric even with a per-row prediction.
+ *  D9. pairs: with max_distance (int32; 256 or more switches it off), ratio_num, ratio_den (int32 in [1, 2^20];
+ *      ratio_den = 0 switches the test off) and cross_check (0 / 1), query row i is kept when idx[i] >= 0,
+ *      dist <= max_distance, (int64)dist * ratio_den < (int64)ratio_num * dist2 and, with cross_check, the
+ *      backward search of idx[i] returns i.  pair_a, pair_b, pair_dist (int32, n_query entries each) hold the
+ *      kept rows' i, idx[i], dist[i] in ascending i; every entry past the count is -1 / -1 / 257; count is one
+ *      int32 in device memory.  With a null gate C is "both rows valid".  No atomics order anything: the result
+ *      is bitwise repeatable.
  * gcs_describe_keypoints queues two kernels whatever n_levels is (the packed resample of P2, then one wave per
  * keypoint) and makes no host synchronisation; the row count is the caller's n_keypoints, so it chains behind a
- * detector with n_keypoints = max_keypoints and the padding.  gcs_match_descriptors queues at most two kernels.
- * Calls on one context must be serialised. */
+ * detector with n_keypoints = max_keypoints and the padding.  gcs_match_descriptors queues at most two kernels,
+ * gcs_match_descriptors_gated two, gcs_match_pairs at most four and one memset (both directions' searches in one
+ * launch, their merges in one, then the keep flags' counts per 256 rows and the stable compaction); neither makes
+ * a host synchronisation.  Calls on one context must be serialised. */
 typedef struct gcs_keypoint_desc_ctx gcs_keypoint_desc_ctx;
 typedef struct gcs_match_ctx gcs_match_ctx;
 #define GCS_DESC_BYTES 32
@@ -1107,6 +1128,57 @@ int gcs_match_ctx_set_stream(gcs_match_ctx* ctx, void* stream);
 int gcs_match_descriptors(gcs_match_ctx* ctx, const gcs_match_inputs* in, gcs_match_outputs* out);
 /* The same on the host; of the config only the capacities are looked at. */
 int gcs_match_descriptors_host(const gcs_match_config* cfg, const gcs_match_inputs* in, gcs_match_outputs* out);
+
+/* D8's gate: device pointers for the device entries, host pointers for the host twins. */
+typedef struct {
+  const float *q_u, *q_v;        /* n_query each; may be null when q_pu and q_pv are given */
+  const int32_t* q_level;        /* n_query, or null: every query row on level 0 */
+  const float *t_u, *t_v;        /* n_train each */
+  const int32_t* t_level;        /* n_train, or null */
+  const float *q_pu, *q_pv;      /* n_query each, or both null: the prediction is q_u, q_v */
+  float radius;                  /* 16; finite, >= 0, level-0 pixels */
+  int32_t max_level_diff;        /* 1; >= 0 */
+} gcs_match_gate;
+
+typedef struct {
+  int32_t *idx, *dist, *dist2;   /* n_query each (D8) */
+  int32_t* n_cand;               /* n_query, or null */
+} gcs_match_gated_outputs;
+
+/* D9's parameters. */
+typedef struct {
+  int32_t max_distance;          /* 64; 256 or more: off */
+  int32_t ratio_num, ratio_den;  /* 4, 5; 1 .. 1048576 each; ratio_den = 0: off */
+  int32_t cross_check;           /* 1 */
+} gcs_match_filter;
+
+typedef struct {
+  int32_t *pair_a, *pair_b, *pair_dist;   /* n_query each (D9) */
+  int32_t* count;                         /* one int32 */
+} gcs_match_pair_outputs;
+
+/* Null pointers, radius 16, max_level_diff 1. */
+int gcs_match_gate_defaults(gcs_match_gate* gate);
+/* 64, 4, 5, 1: the conveniences of gcslam.descriptors.match_descriptors. */
+int gcs_match_filter_defaults(gcs_match_filter* filter);
+/* D8 in one direction.  Queues its kernels on the context's stream and returns.  GCS_ERR_ARG (last_error set) for
+ * what gcs_match_descriptors refuses, a null gate, a radius that is NaN, infinite or negative, a negative
+ * max_level_diff, one of q_pu, q_pv without the other, or a null position array that the counts make necessary
+ * (with n_query > 0 the prediction or q_u and q_v; with n_query > 0 and n_train > 0 also t_u and t_v).  The
+ * context stays usable after a refusal. */
+int gcs_match_descriptors_gated(gcs_match_ctx* ctx, const gcs_match_inputs* in, const gcs_match_gate* gate,
+                                gcs_match_gated_outputs* out);
+/* D8 + D9; a null gate is no gate.  Refuses in addition a null filter, ratio_num outside [1, 1048576], ratio_den
+ * outside [0, 1048576] and a null output array (count is needed even with n_query = 0).  The workspace of
+ * gcs_match_ctx_create covers the backward direction as well: a context serves gcs_match_pairs up to its full
+ * max_query x max_train. */
+int gcs_match_pairs(gcs_match_ctx* ctx, const gcs_match_inputs* in, const gcs_match_gate* gate,
+                    const gcs_match_filter* filter, gcs_match_pair_outputs* out);
+/* The same on the host; of the config only the capacities are looked at. */
+int gcs_match_descriptors_gated_host(const gcs_match_config* cfg, const gcs_match_inputs* in, const gcs_match_gate* gate,
+                                     gcs_match_gated_outputs* out);
+int gcs_match_pairs_host(const gcs_match_config* cfg, const gcs_match_inputs* in, const gcs_match_gate* gate,
+                         const gcs_match_filter* filter, gcs_match_pair_outputs* out);
 
 /* ---------------------------------------------------------------- primitive path: map rendering */
 /* The reference's output side (backend/rendering.py, common/bev_pushforward.py) on the GPU, reading

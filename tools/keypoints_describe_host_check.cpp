@@ -7,7 +7,9 @@
 //   make -C gc-slam_amd keypoints_describe_host_check
 // Exit code 0: every call returned what it should, the rows on and inside the margin are valid and those outside
 // it invalid (NaN, -1, zero bytes), a padded pitch changed nothing, a 1 x 1 image has only invalid rows, n = 0
-// touches nothing, and a set matched against itself finds itself.
+// touches nothing, and a set matched against itself finds itself; the gated search (D8) and the pairs (D9) with a
+// context of exactly the call's counts, n = 0 on either side included: candidates only among valid, finite rows, the
+// pairs ascending and consistent with the search, the tails filled, a refusal touching nothing.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -166,6 +168,102 @@ int match(int n_q, int n_t, bool self, bool bins) {
   return rc;
 }
 
+// The two gated host twins over n_q x n_t rows, every array in a heap block of exactly its length, the context's
+// capacity exactly the counts: positions on a 12-pixel lattice with radius 8 (few candidates per row), some rows not
+// finite, some invalid.  With `self` the train set is the query set, so every valid, finite row pairs with itself.
+int gated(int n_q, int n_t, bool self, bool levels, bool predicted) {
+  gcs_match_config cfg;
+  gcs_match_config_defaults(&cfg);
+  cfg.max_query = n_q ? n_q : 1;
+  cfg.max_train = n_t ? n_t : 1;
+  auto bytes = [](int n, size_t each) { return malloc(n ? n * each : 1); };
+  uint8_t* q = (uint8_t*)bytes(n_q, GCS_DESC_BYTES);
+  uint8_t* t = (uint8_t*)bytes(n_t, GCS_DESC_BYTES);
+  int32_t *qb = (int32_t*)bytes(n_q, 4), *tb = (int32_t*)bytes(n_t, 4), *ql = (int32_t*)bytes(n_q, 4), *tl = (int32_t*)bytes(n_t, 4);
+  float *qu = (float*)bytes(n_q, 4), *qv = (float*)bytes(n_q, 4), *tu = (float*)bytes(n_t, 4), *tv = (float*)bytes(n_t, 4);
+  float *pu = (float*)bytes(n_q, 4), *pv = (float*)bytes(n_q, 4);
+  int32_t* out[8];
+  for (int k = 0; k < 8; ++k) out[k] = (int32_t*)bytes(n_q, 4);
+  int32_t* count = (int32_t*)malloc(4);
+  for (int i = 0; i < GCS_DESC_BYTES * n_q; ++i) q[i] = next_byte();
+  for (int i = 0; i < GCS_DESC_BYTES * n_t; ++i) t[i] = self ? q[i] : next_byte();
+  for (int i = 0; i < n_q; ++i) {
+    qb[i] = i % 5 == 0 ? -1 : i % 32;
+    ql[i] = i % 3;
+    qu[i] = i % 11 == 3 ? NAN : (float)(12 * (i % 9));
+    qv[i] = i % 13 == 4 ? INFINITY : (float)(12 * (i / 9 % 9));
+    pu[i] = qu[i] + 3.0f;   // the prediction: a motion of (3, -2) the train rows do not have
+    pv[i] = qv[i] - 2.0f;
+  }
+  for (int j = 0; j < n_t; ++j) {
+    tb[j] = self ? qb[j] : (j % 7 == 0 ? -1 : j % 32);
+    tl[j] = self ? ql[j] : j % 4;
+    tu[j] = self ? qu[j] : (float)(12 * (j % 9) + 3);
+    tv[j] = self ? qv[j] : (float)(12 * (j / 9 % 9) - 2);
+  }
+  gcs_match_inputs in = {n_q, n_t, n_q ? q : nullptr, n_t ? t : nullptr, n_q ? qb : nullptr, n_t ? tb : nullptr};
+  gcs_match_gate gate;
+  gcs_match_gate_defaults(&gate);
+  int rc = gate.radius == 16.0f && gate.max_level_diff == 1 && !gate.q_u && !gate.q_pv ? GCS_OK : -120;
+  gate.radius = 8.0f;
+  if (n_q) {
+    gate.q_u = qu;
+    gate.q_v = qv;
+    gate.q_level = levels ? ql : nullptr;
+    if (predicted && !self) {
+      gate.q_pu = pu;
+      gate.q_pv = pv;
+    }
+  }
+  if (n_t) {
+    gate.t_u = tu;
+    gate.t_v = tv;
+    gate.t_level = levels ? tl : nullptr;
+  }
+  gcs_match_filter f;
+  gcs_match_filter_defaults(&f);
+  if (f.max_distance != 64 || f.ratio_num != 4 || f.ratio_den != 5 || f.cross_check != 1) rc = -121;
+  f.ratio_den = 0;   // (equal rows at one place would fail the ratio test)
+  gcs_match_gated_outputs go = {n_q ? out[0] : nullptr, n_q ? out[1] : nullptr, n_q ? out[2] : nullptr, n_q ? out[3] : nullptr};
+  gcs_match_pair_outputs po = {n_q ? out[4] : nullptr, n_q ? out[5] : nullptr, n_q ? out[6] : nullptr, count};
+  *count = -7;
+  if (rc == GCS_OK) rc = gcs_match_descriptors_gated_host(&cfg, &in, &gate, &go);
+  if (rc == GCS_OK) rc = gcs_match_pairs_host(&cfg, &in, &gate, &f, &po);
+  if (rc == GCS_OK && (*count < 0 || *count > n_q)) rc = -122;
+  int with_cand = 0;
+  for (int i = 0; i < n_q && rc == GCS_OK; ++i) {
+    const int32_t idx = out[0][i], dist = out[1][i], n_cand = out[3][i];
+    const bool finite = std::isfinite(qu[i]) && std::isfinite(qv[i]);
+    with_cand += n_cand > 0;
+    if (n_cand < 0 || n_cand > n_t || (n_cand == 0) != (idx == -1) || (idx == -1) != (dist == GCS_MATCH_NONE)) rc = -123;
+    else if ((qb[i] < 0 || !finite) && n_cand != 0) rc = -124;
+    else if (idx >= n_t || (idx >= 0 && tb[idx] < 0)) rc = -125;
+    else if (n_cand == 1 && out[2][i] != GCS_MATCH_NONE) rc = -126;
+    else if (self && qb[i] >= 0 && finite && (idx > i || dist != 0)) rc = -127;
+    const int32_t a = out[4][i], b = out[5][i], d = out[6][i];
+    if (rc != GCS_OK) break;
+    if (i < *count ? (a < 0 || a >= n_q || b != out[0][a] || d != out[1][a] || (i > 0 && a <= out[4][i - 1]))
+                   : (a != -1 || b != -1 || d != GCS_MATCH_NONE))
+      rc = -128;
+  }
+  if (rc == GCS_OK && self && n_q >= 30 && *count < n_q / 2) rc = -129;
+  if (rc == GCS_OK && !self && n_q >= 30 && n_t >= 30 && with_cand == 0) rc = -130;   // the lattice gives candidates
+  // a refusal leaves the outputs alone and the next call works
+  if (rc == GCS_OK && n_q) {
+    gate.radius = -1.0f;
+    const int32_t before = *count;
+    if (gcs_match_pairs_host(&cfg, &in, &gate, &f, &po) != GCS_ERR_ARG || *count != before) rc = -131;
+    if (gcs_match_descriptors_gated_host(&cfg, &in, &gate, &go) != GCS_ERR_ARG) rc = -132;
+    gate.radius = 8.0f;
+    if (rc == GCS_OK) rc = gcs_match_pairs_host(&cfg, &in, nullptr, &f, &po);   // no gate
+    if (rc == GCS_OK && *count > n_q) rc = -133;
+  }
+  free(q); free(t); free(qb); free(tb); free(ql); free(tl); free(qu); free(qv); free(tu); free(tv); free(pu); free(pv);
+  for (int k = 0; k < 8; ++k) free(out[k]);
+  free(count);
+  return rc;
+}
+
 int g_failed = 0;
 void expect(const char* what, int rc, int n, int n_valid, bool ok) {
   printf("%-56s rc %d  rows %d  valid %d  %s\n", what, rc, n, n_valid, ok ? "ok" : "UNEXPECTED");
@@ -227,6 +325,19 @@ int main() {
   for (int bins = 0; bins <= 1; ++bins) {
     snprintf(name, sizeof(name), "match 300 rows against themselves%s", bins ? " with bins" : "");
     const int rc = match(300, 300, true, bins);
+    expect(name, rc, 300, 300, rc == GCS_OK);
+  }
+  // the gated search and the pairs: the context's capacity is exactly the counts of every call
+  for (const auto& s : sizes)
+    for (int variant = 0; variant < 4; ++variant) {
+      snprintf(name, sizeof(name), "gated and pairs %d x %d%s%s", s[0], s[1], variant & 1 ? " with levels" : "",
+               variant & 2 ? " predicted" : "");
+      const int rc = gated(s[0], s[1], false, variant & 1, variant & 2);
+      expect(name, rc, s[0], s[1], rc == GCS_OK);
+    }
+  for (int levels = 0; levels <= 1; ++levels) {
+    snprintf(name, sizeof(name), "gated and pairs, 300 rows against themselves%s", levels ? " with levels" : "");
+    const int rc = gated(300, 300, true, levels, false);
     expect(name, rc, 300, 300, rc == GCS_OK);
   }
   printf(g_failed ? "%d unexpected\n" : "all as expected\n", g_failed);

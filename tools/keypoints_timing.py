@@ -24,10 +24,16 @@ each route after its own warm-up, the median of REPEAT calls:
   match             DescriptorMatcher.queue of the frame's descriptors against those of the frame moved by (5, 3)
                     pixels, 512 x 512 and 4,096 x 4,096 (nearest and second nearest of every row, one way), and
                     `match_descriptors` with its defaults (both ways, the filters and the result's length read back)
+  match_gated       DescriptorMatcher.queue_gated of the same sets with the keypoints' positions and levels and the
+                    default GateConfig (radius 16, one level apart), one way; to be read against `match_queue`
+  match_pairs       `match_pairs` without a gate and with the default gate (both searches, the filters, the cross check
+                    and the compaction on the device, one wait for the count); to be read against `match_descriptors`
 
 --desc prints the describe and match lines and GridDetector's `queue` and `detect` at both sizes only; --grid-only the
 GridDetector lines only (with GCSLAM_LIB naming a build of before the describer, for a same-session comparison).
---profile-desc K runs the describer's and the matcher's `queue` at max_keypoints K for a kernel trace.
+--profile-desc K runs the describer's and the matcher's `queue` at max_keypoints K for a kernel trace; --profile-gate K
+the matcher's `queue`, `queue_gated` and both `match_pairs`.  --no-gate leaves the gated routes out (with GCSLAM_LIB
+naming a build of before them).
 
 --profile runs `detect` only, --profile-pyramid `pyramid_detect` only and --profile-grid K the pyramid's and the
 grid's `detect` at max_keypoints K, WARMUP + REPEAT times, for a kernel trace taken from outside.  Prints one
@@ -62,6 +68,8 @@ def main():
     ap.add_argument("--desc", action="store_true")
     ap.add_argument("--grid-only", action="store_true")
     ap.add_argument("--profile-desc", type=int, default=0, metavar="K")
+    ap.add_argument("--profile-gate", type=int, default=0, metavar="K")
+    ap.add_argument("--no-gate", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -112,7 +120,7 @@ def main():
         print(json.dumps(dict(profile_calls=WARMUP + REPEAT, max_keypoints=args.profile_grid)))
         return
 
-    def desc_lines(caps, grid_only=False, profile=False):
+    def desc_lines(caps, grid_only=False, profile=False, gate=True, profile_gate=False):
         """The describe and match lines (and GridDetector's own) at every cap."""
         res = {}
         moved = torch.roll(rgb_d, (3, 5), (0, 1)).contiguous()
@@ -132,10 +140,21 @@ def main():
                           ("describe_keypoints", lambda: D.describe_keypoints(rgb_d, ka, D.DescriptorConfig(max_keypoints=cap))),
                           ("match_queue", lambda: m.queue(da.desc, db.desc, da.angle_bin, db.angle_bin)),
                           ("match_descriptors", lambda: D.match_descriptors(da, db))] + routes
-            if profile:
+                if gate:
+                    gated = D.match_pairs(da, db, ka, kb)
+                    r.update(pairs_no_gate=int(D.match_pairs(da, db)[0].shape[0]), pairs_gated=int(gated[0].shape[0]))
+                    routes = [("match_gated", lambda: m.queue_gated(da.desc, db.desc, ka, kb, q_bin=da.angle_bin, t_bin=db.angle_bin)),
+                              ("match_pairs", lambda: D.match_pairs(da, db)),
+                              ("match_pairs_gated", lambda: D.match_pairs(da, db, ka, kb))] + routes
+            if profile_gate:
                 for _ in range(WARMUP + REPEAT):
-                    routes[0][1]()
-                    routes[2][1]()
+                    for name in ("match_queue", "match_gated", "match_pairs", "match_pairs_gated"):
+                        dict(routes)[name]()
+                torch.cuda.synchronize()
+            elif profile:
+                for _ in range(WARMUP + REPEAT):
+                    dict(routes)["describe_queue"]()
+                    dict(routes)["match_queue"]()
                 torch.cuda.synchronize()
             else:
                 for name, _ in routes:
@@ -149,10 +168,10 @@ def main():
             g.close()
         return res
 
-    if args.desc or args.grid_only or args.profile_desc:
-        caps = (args.profile_desc,) if args.profile_desc else (512, 4096)
+    if args.desc or args.grid_only or args.profile_desc or args.profile_gate:
+        caps = (args.profile_desc or args.profile_gate,) if args.profile_desc or args.profile_gate else (512, 4096)
         out = dict(width=W, height=H, warmup=WARMUP, repeat=REPEAT, lib=os.environ.get("GCSLAM_LIB", "in-tree"))
-        out.update(desc_lines(caps, args.grid_only, bool(args.profile_desc)))
+        out.update(desc_lines(caps, args.grid_only, bool(args.profile_desc), not args.no_gate, bool(args.profile_gate)))
         print(json.dumps(out))
         return
 
