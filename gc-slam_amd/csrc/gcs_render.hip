@@ -51,9 +51,17 @@ GCS_HD void rn_prepare_row(int i, const RnRows& in, const RnViews& vw, const RnP
   const double* p = in.pos + 3 * (size_t)i;
   const double* S = in.cov + 9 * (size_t)i;
   bool ok = !in.valid || in.valid[i] != 0;
-  // with fBm on, the lattice index of x * 2^octave (octave < 16) has to fit an int64 (a NaN position fails the
-  // test too; with fBm off a non-finite position falls out at the pushforward)
+  // a position that is not finite has no pixel in any view: the whole row is dropped, fBm on or off
+  ok = ok && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
+  // with fBm on, the lattice index of x * 2^octave (octave < 16) has to fit an int64
   if (a.fbm_scale > 0.0) ok = ok && fabs(p[0]) < 0x1p46 && fabs(p[1]) < 0x1p46;
+  // a NaN among the shading's inputs reaches every view's colour (np.clip hands it on): the whole row is dropped
+  if (ok) {
+    const double* d = in.dir + 3 * (size_t)i;
+    const double* c = in.col + 3 * (size_t)i;
+    const double k = in.kappa[i], t = in.intensity && a.int_scale > 0.0 ? in.intensity[i] : 0.0;
+    ok = !(d[0] != d[0] || d[1] != d[1] || d[2] != d[2] || c[0] != c[0] || c[1] != c[1] || c[2] != c[2] || k != k || t != t);
+  }
   double alpha = 0.0, fb = 0.0, mod = 1.0;
   if (ok) {
     alpha = rn_opacity(rn_logdet3(S), a.gamma, a.logdet0, a.alpha_min);
@@ -63,18 +71,24 @@ GCS_HD void rn_prepare_row(int i, const RnRows& in, const RnViews& vw, const RnP
     fb = rn_fbm(p[0], p[1], a.fbm_octaves, a.fbm_gain, a.fbm_seed);
     mod = (1.0 - a.fbm_scale) + a.fbm_scale * fb;
   }
-  o.alphas[i] = ok ? alpha : 0.0;
-  if (o.fbm) o.fbm[i] = ok ? fb : 0.0;
+  bool kept = false;   // by some view
   for (int v = 0; v < vw.n; ++v) {
     const size_t k = (size_t)v * N + (size_t)i;
     double mu2[2] = {0.0, 0.0}, Si[4] = {0.0, 0.0, 0.0, 0.0}, r = -INFINITY, c[3] = {0.0, 0.0, 0.0};
     if (ok && rn_push_row(p, S, vw.P[v], vw.off[v], a.eps, mu2, Si, &r)) {
       const double s = rn_shade_one_lobe(vw.vn[v], in.dir + 3 * (size_t)i, in.kappa[i], in.intensity != nullptr,
                                          in.intensity ? in.intensity[i] : 0.0, a);
-      for (int j = 0; j < 3; ++j) c[j] = fmin(fmax(in.col[3 * (size_t)i + j] * s, 0.0), 1.0) * mod;
-      if (!(isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]))) {
+      bool has_nan = false;   // fmax / fmin return their other argument for a NaN: np.clip would hand it on
+      for (int j = 0; j < 3; ++j) {
+        const double raw = in.col[3 * (size_t)i + j] * s;
+        has_nan = has_nan || raw != raw;
+        c[j] = fmin(fmax(raw, 0.0), 1.0) * mod;
+      }
+      if (has_nan || !(isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]))) {
         r = -INFINITY;
         mu2[0] = mu2[1] = Si[0] = Si[1] = Si[2] = Si[3] = c[0] = c[1] = c[2] = 0.0;
+      } else {
+        kept = true;
       }
     }
     o.means[2 * k] = mu2[0]; o.means[2 * k + 1] = mu2[1];
@@ -82,6 +96,9 @@ GCS_HD void rn_prepare_row(int i, const RnRows& in, const RnViews& vw, const RnP
     o.radii[k] = r;
     for (int j = 0; j < 3; ++j) o.colors[3 * k + j] = c[j];
   }
+  // a row that no view keeps is an invalid row's record throughout; one that some views drop keeps its own
+  o.alphas[i] = kept ? alpha : 0.0;
+  if (o.fbm) o.fbm[i] = kept ? fb : 0.0;
 }
 
 __global__ __launch_bounds__(kRnThreads) void k_rn_prepare(RnRows in, RnViews vw, RnParams a, gcs_render_splats o) {
@@ -279,14 +296,14 @@ RnParams rn_params(const gcs_render_config& c, const gcs_render_prepare_inputs& 
   return a;
 }
 
-// rendering.py:135-136: v / (|v| + eps)
-void rn_views(const gcs_render_config& c, const gcs_render_prepare_inputs& in, RnViews* vw) {
+// rendering.py:135-136: v / (|v| + eps), eps the shading's own default
+void rn_views(const gcs_render_prepare_inputs& in, RnViews* vw) {
   vw->n = in.n_views;
   for (int v = 0; v < in.n_views; ++v) {
     for (int j = 0; j < 6; ++j) vw->P[v][j] = in.P_pix[6 * v + j];
     for (int j = 0; j < 2; ++j) vw->off[v][j] = in.offsets[2 * v + j];
     const double* d = in.view_dirs + 3 * v;
-    const double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) + c.eps;
+    const double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) + kRnNormEps;
     for (int j = 0; j < 3; ++j) vw->vn[v][j] = d[j] / nrm;
   }
 }
@@ -360,7 +377,7 @@ int rn_check_image(gcs_render_ctx* c, int n_views, int n_rows, int width, int he
 void rn_queue_prepare(gcs_render_ctx* c, const gcs_render_prepare_inputs& in, const gcs_render_splats& o) {
   if (in.n_rows == 0) return;
   RnViews vw;
-  rn_views(c->cfg, in, &vw);
+  rn_views(in, &vw);
   RnRows rows{in.positions, in.covariances, in.directions, in.kappas, in.colors, in.intensity, in.valid_mask, in.n_rows};
   hipLaunchKernelGGL(k_rn_prepare, dim3((in.n_rows + kRnThreads - 1) / kRnThreads), dim3(kRnThreads), 0, c->stream, rows,
                      vw, rn_params(c->cfg, in), o);
@@ -446,7 +463,7 @@ int gcs_render_ctx_set_stream(gcs_render_ctx* c, void* stream) {
 int gcs_render_prepare_host(const gcs_render_config* cfg, const gcs_render_prepare_inputs* in, gcs_render_splats* out) {
   if (rn_check_config(cfg) || !out || rn_check_prepare(in, out)) return GCS_ERR_ARG;
   RnViews vw;
-  rn_views(*cfg, *in, &vw);
+  rn_views(*in, &vw);
   const RnParams a = rn_params(*cfg, *in);
   RnRows rows{in->positions, in->covariances, in->directions, in->kappas, in->colors, in->intensity, in->valid_mask,
               in->n_rows};

@@ -16,12 +16,16 @@
 namespace gcs {
 
 struct RnParams {
-  double gamma, logdet0, alpha_min, eps;        // opacity_from_logdet, the radius floor and the norms' eps
+  double gamma, logdet0, alpha_min, eps;        // opacity_from_logdet and the radius floor
   double int_scale, int_max, kappa_max;         // kappa_modulated_by_intensity
   double fbm_gain, fbm_scale;
   int32_t fbm_octaves;
   int64_t fbm_seed;
 };
+
+// vmf_shading_multi_lobe's and kappa_modulated_by_intensity's own eps (rendering.py:102,126): the composed
+// call leaves it at its default, whatever the config's eps (the radius floor of splat_indices_for_tile) is.
+constexpr double kRnNormEps = 1e-12;
 
 // rendering.py:167-170.  Python's integers do not wrap; the masks keep the low 31 bits, which
 // two's-complement wrap-around leaves untouched, so unsigned 64-bit arithmetic gives the same value.
@@ -77,17 +81,17 @@ GCS_HD double rn_logdet3(const double* S) {
 }
 
 GCS_HD double rn_kappa_modulated(double kappa, double intensity, const RnParams& a) {   // :96-114
-  if (a.int_scale <= 0.0 || a.int_max <= a.eps) return kappa;
-  double t = intensity / fmax(a.int_max, a.eps);
+  if (a.int_scale <= 0.0 || a.int_max <= kRnNormEps) return kappa;
+  double t = intensity / fmax(a.int_max, kRnNormEps);
   t = fmax(0.0, fmin(1.0, t));
   return fmin(kappa * (1.0 + a.int_scale * t), a.kappa_max);
 }
 
 // vmf_shading_multi_lobe with one lobe and uniform pi (= 1): exp(k (mu . v - 1)) / (1 + k).
-// vn: the view direction already divided by (|v| + eps).
+// vn: the view direction already divided by (|v| + kRnNormEps).
 GCS_HD double rn_shade_one_lobe(const double* vn, const double* dir, double kappa, bool has_int, double intensity,
                                 const RnParams& a) {
-  const double nrm = sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]) + a.eps;
+  const double nrm = sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]) + kRnNormEps;
   const double m0 = dir[0] / nrm, m1 = dir[1] / nrm, m2 = dir[2] / nrm;
   double k = kappa;
   if (a.int_scale > 0.0 && has_int) k = rn_kappa_modulated(k, intensity, a);

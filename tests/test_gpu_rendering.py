@@ -123,21 +123,7 @@ def test_render_map_view_end_to_end(name):
 
 
 # ---------------------------------------------------------------------- determinism and larger shapes
-def _scene(rng, n, centres, spread, width, height):
-    """n rows on a width x height px image (1 px/m at phi = 0): uniform background plus clusters."""
-    pos = np.stack([rng.uniform(-0.5 * width, 0.5 * width, n), rng.uniform(-0.5 * height, 0.5 * height, n),
-                    rng.uniform(0.0, 0.5, n)], 1)
-    k = 0
-    for (cx, cy), m in centres:
-        pos[k:k + m, 0] = cx - 0.5 * width + rng.uniform(-spread, spread, m)
-        pos[k:k + m, 1] = cy - 0.5 * height + rng.uniform(-spread, spread, m)
-        k += m
-    A = rng.normal(size=(n, 3, 3)) * np.array([1.2, 1.2, 0.1])
-    cov = A @ A.transpose(0, 2, 1) + 0.01 * np.eye(3)
-    perm = rng.permutation(n)
-    return dict(positions=pos[perm], covariances=cov[perm], directions=rng.normal(size=(n, 3)) + [0.0, -0.2, 1.0],
-                kappas=rng.uniform(0.1, 4.0, n), colors=rng.uniform(0.0, 1.0, (n, 3)),
-                valid_mask=rng.uniform(size=n) > 0.05)
+_scene = RU.random_scene
 
 
 def test_two_calls_are_bitwise_equal():
@@ -157,23 +143,7 @@ def test_two_calls_are_bitwise_equal():
     assert int(a.tile_counts.max()) == 48 and a.images.any()
 
 
-def _check_against_restatement(sc, cfg, V, W, H):
-    res = R.render_map_view(RU.device_view(sc), bev=R.BEVPushforwardConfig(n_views=V), cfg=cfg, width=W, height=H,
-                            pixels_per_metre=1.0, centre_xy=(0.0, 0.0), want_splats=True)
-    s = {k: cpu(v) for k, v in res.splats.items()}
-    P_pix, off, vd = R.view_geometry(R.BEVPushforwardConfig(n_views=V), W, H, 1.0, (0.0, 0.0))
-    host = R.prepare_splats_host(sc["positions"], sc["covariances"], sc["directions"], sc["kappas"], sc["colors"],
-                                 sc["valid_mask"], P_pix, off, vd, cfg=cfg)
-    for k in ("means", "Sigmas_inv", "alphas", "colors"):     # the kernel's rows against the host build of them
-        np.testing.assert_allclose(s[k], host[k], rtol=1e-12, atol=1e-300, err_msg=k)
-    assert np.array_equal(s["radii"] == -np.inf, host["radii"] == -np.inf)
-    # same record in, same decisions out: the comparisons and dist^2 are the same f64 operations
-    idx, cnt = RU.bin_tiles_np(s["means"], s["radii"], W, H, cfg.tile_size, cfg.max_splats_per_tile)
-    assert np.array_equal(cpu(res.tile_counts), cnt) and np.array_equal(cpu(res.tile_indices), idx)
-    tiles = RU.render_tiles_np(s["means"], s["Sigmas_inv"], s["alphas"], s["colors"], idx, cnt, W, H, cfg.tile_size,
-                               cfg.ewa_log_clip)
-    np.testing.assert_allclose(cpu(res.images), RU.image_from_tiles(tiles, W, H), rtol=1e-9, atol=1e-12)
-    return cnt
+_check_against_restatement = RU.check_against_restatement
 
 
 def test_n4097_two_clusters_in_one_tile_cap64():
